@@ -16,8 +16,13 @@ all-gather over RCCL per PageRank iteration.  Rank 0 prints ONE JSON line.
 Steps are pipelined over two HIP streams (two shard states over the same resident metrics): step
 i+1's HBM-bound scoring runs while step i's latency-bound PageRank iterates (the scoring kernels
 themselves stay one at a time, ordered by an event), and step i's top-10 is merged on the host
-after step i+1 has been enqueued.  Every step still does all of its work;
-`e2e_rca_latency_ms` is measured separately, one step at a time.
+after step i+1 has been enqueued.  Every step still does all of its work.
+
+A plain run sets up, warms up, times --steps steps and prints the line (`value`, `ms_per_step`).
+`--full` adds what takes runs of its own: `e2e_rca_latency_ms` (one step at a time) and the
+scoring kernel alone, the verification against the C oracle, the spread-model recall, the CPU
+baseline and the correlation leg.  `--dump-outputs DIR` writes the last timed step's results as
+DIR/<name>.npy, so that two builds can be compared output for output on the same seeded inputs.
 """
 import argparse
 import json
@@ -84,8 +89,17 @@ def parse(argv=None):
                     help="after the timed steps, one unpipelined step per rank with a HIP event around every "
                          "launch (scoring, PageRank init / folded step / exchange / finish, key + top-k) and roctx "
                          "ranges for rocprofv3 --marker-trace; per-kernel times go to the JSON line's 'profile'")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything beside the headline figure: the unpipelined "
+                         "latency steps (e2e_rca_latency_ms, the scoring kernel alone), the oracle verification, the "
+                         "spread-model recall, the CPU baseline and the correlation leg (each still has its --no-* "
+                         "switch); without it the run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed as DIR/<name>.npy (float32 / "
+                         "float64; rank 0 writes the whole mesh's arrays): the top-k pods and their keys, every pod's "
+                         "score / n_exceed / flags and fixed-point rank; a fixed seeded sample of the pods above 64 MB")
     a = ap.parse_args(argv)
-    a.corr_pods = 0 if a.no_corr else (a.pods if a.corr_pods is None else a.corr_pods)
+    a.corr_pods = 0 if a.no_corr or not a.full else (a.pods if a.corr_pods is None else a.corr_pods)
     return a
 
 
@@ -282,6 +296,39 @@ def gather_rows(t, n_max, world):
     out = torch.empty(world * n_max, dtype=t.dtype, device=t.device)
     all_gather_flat(out, pad, world)
     return out
+
+
+DUMP_BYTES = 64 * 2 ** 20  # --dump-outputs writes at most this much
+DUMP_ROW_BYTES = 4 + 4 + 4 + 8 + 8  # score, n_exceed, flags (float32), ppr_rank, sample_pods (float64) per pod
+
+
+def dump_outputs(out_dir, shard, top_idx, top_key, part, ppart, rank):
+    """--dump-outputs: the last timed step's results as <name>.npy, every rank's rows gathered to
+    rank 0 in pod order.  top_idx / top_key are what the step returns (the root-cause pods, best
+    first, and their keys' r*q values); score / n_exceed / flags are the scoring's outputs per pod
+    and ppr_rank the PageRank fixed point (int64 units of 2^-60, rounded to float64).  When the
+    per-pod arrays exceed DUMP_BYTES they hold a seeded sample of the pods, listed in sample_pods."""
+    from krca.rca import key_to_score
+    lo, hi, n_max = part.range(rank)
+    plo, phi, p_slot = ppart.range(rank if ppart.world > 1 else 0)
+    so = shard.score_out
+    cols = {k: part.unpad(gather_rows(so[k][:hi - lo], n_max, part.world).cpu().numpy())
+            for k in ("score", "n_exceed", "flags")}
+    cols["ppr_rank"] = ppart.unpad(gather_rows(shard.r[:phi - plo], p_slot, ppart.world).cpu().numpy())
+    if rank != 0:
+        return
+    n = len(cols["score"])
+    keep = (DUMP_BYTES - 4096) // DUMP_ROW_BYTES
+    pods = np.arange(n) if n <= keep else np.sort(np.random.default_rng(0).choice(n, size=keep, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    out = {"top_idx": np.asarray(top_idx, np.float64), "top_key": key_to_score(top_key).astype(np.float64),
+           "score": cols["score"][pods].astype(np.float32), "n_exceed": cols["n_exceed"][pods].astype(np.float32),
+           "flags": cols["flags"][pods].astype(np.float32), "ppr_rank": cols["ppr_rank"][pods].astype(np.float64),
+           "sample_pods": pods.astype(np.float64)}
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    log(f"bench: wrote {len(out)} arrays ({sum(a.nbytes for a in out.values()) / 2 ** 20:.1f} MiB, {len(pods)} of "
+        f"{n} pods) to {out_dir}")
 
 
 def pmc_traffic(args, bytes_alg, world):
@@ -673,9 +720,12 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    # end-to-end latency of one step (scores -> PageRank -> top-10 on the host), not pipelined
+    if args.dump_outputs:  # the last timed step ran on pipeline slot (steps - 1) % n_pipe
+        dump_outputs(args.dump_outputs, shards[(args.steps - 1) % n_pipe], top_idx, top_key, part, ppart, rank)
+    # end-to-end latency of one step (scores -> PageRank -> top-10 on the host), not pipelined (--full)
     lat = []
-    ev_solo = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(5)]
+    ev_solo = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+               for _ in range(5 if args.full else 0)]
     for e_solo in ev_solo:
         if world > 1:
             dist.barrier()
@@ -685,13 +735,15 @@ def main():
             top_idx, top_key = step.run(score_events=e_solo)
         torch.cuda.synchronize()
         lat.append(time.perf_counter() - t1)
-    solo_ms = float(np.median([a.elapsed_time(b) for a, b in ev_solo]))
-    latency_ms = float(np.median(lat)) * 1e3
-    latency_p95_ms = float(np.percentile(lat, 95)) * 1e3
-    if world > 1:
-        t = torch.tensor([latency_ms], dtype=torch.float64, device="cuda")
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        latency_ms = float(t.item())
+    solo_ms = latency_ms = latency_p95_ms = None
+    if args.full:
+        solo_ms = float(np.median([a.elapsed_time(b) for a, b in ev_solo]))
+        latency_ms = float(np.median(lat)) * 1e3
+        latency_p95_ms = float(np.percentile(lat, 95)) * 1e3
+        if world > 1:
+            t = torch.tensor([latency_ms], dtype=torch.float64, device="cuda")
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            latency_ms = float(t.item())
     score_ms = float(np.mean([a.elapsed_time(b) for a, b in ev]))
     prof = profile_step(step, streams[0], world) if args.profile else None
 
@@ -742,9 +794,9 @@ def main():
                          "algorithmic_bytes_per_launch": bytes_score, "per_rank": True,
                          "avg_launch_ms": score_ms,
                          # the timed steps are pipelined: each scoring launch shares the GPU with the
-                         # previous step's PageRank; the same kernel alone (latency steps, same run):
+                         # previous step's PageRank; the same kernel alone (--full's latency steps, same run):
                          "solo_avg_launch_ms": solo_ms,
-                         "solo_frac": bytes_score / (solo_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                         "solo_frac": bytes_score / (solo_ms * 1e-3) / 1e9 / HBM_PEAK_GBS if solo_ms else None,
                          "aggregate": {"achieved": agg_achieved, "peak": HBM_PEAK_GBS * world, "unit": "GB/s",
                                        "frac": agg_achieved / (HBM_PEAK_GBS * world),
                                        "bytes_per_step": score_bytes(args.pods, args.metrics, args.tsteps),
@@ -756,7 +808,7 @@ def main():
         }
 
     # ---- verification (not timed): bit-exact PageRank / top-10 vs the C oracle, any N -------
-    if not args.no_verify:
+    if args.full and not args.no_verify:
         try:
             v = verify_step(args, cfg, mesh, shard, x, part, ppart, rank)
             if rank == 0:
@@ -768,7 +820,7 @@ def main():
             result["verify"] = v
 
     # ---- the ranking on the spread failure model (untimed, C2 size, rank 0) ------------------
-    if rank == 0 and not args.no_verify:
+    if rank == 0 and args.full and not args.no_verify:
         try:
             # three meshes (the C2 ablation's seeds): the mean is the recall the ranking is held to
             runs = [spread_recall(eng, cfg, args.seed + k) for k in range(3)]
@@ -782,7 +834,7 @@ def main():
             result["spread_check"] = {"error": repr(e)[:500]}
 
     # ---- CPU baseline: the C restatement on the host cores, bounded sample (rank 0) -------
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         try:
             result["cpu_baseline"] = cpu_baseline(args, cfg, mesh, shard, x, n_loc)
         except Exception as e:

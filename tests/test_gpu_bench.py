@@ -19,15 +19,17 @@ from conftest import ROOT
 
 pytestmark = pytest.mark.gpu
 
-ARGS = ["--pods", "20000", "--edges", "400000", "--steps", "2", "--warmup", "1", "--cpu-warmup", "1", "--cpu-runs", "2",
-        "--corr-runs", "1"]
+ARGS = ["--full", "--pods", "20000", "--edges", "400000", "--steps", "2", "--warmup", "1", "--cpu-warmup", "1",
+        "--cpu-runs", "2", "--corr-runs", "1"]
+# a plain run: set-up, warm-up, the timed steps and the line (an odd pod count)
+PLAIN = ["--pods", "5003", "--edges", "100000", "--steps", "3", "--warmup", "1"]
 
 
-def run_bench(n, extra=()):
+def run_bench(n, extra=(), args=ARGS):
     env = dict(os.environ, KRCA_BENCH_BACKEND="gloo")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), *ARGS, *extra], env=env,
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), *args, *extra], env=env,
                        capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-4000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -80,3 +82,29 @@ def test_bench_gpus_2_runs_two_ranks():
     n = one["ppr_iters_run"] + 1
     assert prof["krca_ppr_shard_step_folded"]["launches"] == n and prof["krca_rolling_score"]["launches"] == 1
     assert prof["krca_ppr_shard_finish"]["launches"] == 1 and prof["exchange"]["launches"] == n + 1
+
+
+def test_plain_run_times_its_steps_and_dumps_them(tmp_path):
+    """Without --full the line holds the headline figure only (no latency steps, verification, CPU
+    baseline or correlation leg), --steps sets the timed steps, and --dump-outputs writes the last
+    timed step's results: float32 / float64 arrays, the top-10 of the line, identical from run to run."""
+    import numpy as np
+    a, b = str(tmp_path / "a"), str(tmp_path / "b")
+    one = run_bench(1, ["--dump-outputs", a], PLAIN)
+    two = run_bench(1, ["--dump-outputs", b], PLAIN)
+    assert one["steps"] == 3 and one["warmup"] == 1 and one["unit"] == "pod·timesteps/s" and one["higher_is_better"]
+    assert one["ms_per_step"] > 0 and abs(one["value"] * one["ms_per_step"] * 1e-3 / (5003 * 1440) - 1) < 1e-9
+    for key in ("verify", "cpu_baseline", "corr", "spread_check", "profile"):
+        assert key not in one, key
+    assert one["e2e_rca_latency_ms"] is None and one["roofline"]["solo_avg_launch_ms"] is None
+    names = sorted(os.listdir(a))
+    assert names == sorted(n + ".npy" for n in ("top_idx", "top_key", "score", "n_exceed", "flags", "ppr_rank",
+                                                "sample_pods"))
+    out = {n[:-4]: np.load(os.path.join(a, n)) for n in names}
+    assert all(v.dtype in (np.float32, np.float64) for v in out.values())
+    assert sum(v.nbytes for v in out.values()) <= 64 * 2 ** 20
+    assert out["top_idx"].tolist() == one["rca_top10"] == two["rca_top10"] and np.all(np.diff(out["top_key"]) <= 0)
+    assert all(len(out[n]) == 5003 for n in ("score", "n_exceed", "flags", "ppr_rank", "sample_pods"))
+    assert out["score"].max() > 0 and out["ppr_rank"].sum() > 0 and out["n_exceed"].max() > 0
+    for n in names:
+        assert np.array_equal(out[n[:-4]], np.load(os.path.join(b, n))), n

@@ -13,6 +13,6 @@ case $rc in 0|1) ;; *) exit $rc;; esac
 timeout -k 10 150 python -u -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1
 rc=$?; echo "smoke EXIT=$rc" >> $OUT/status; tail -2 $OUT/smoke.log
 [ $rc -eq 0 ] || exit $rc
-timeout -k 10 450 python -u bench.py --steps 10 --warmup 2 > $OUT/bench.json 2> $OUT/bench.err
+timeout -k 10 450 python -u bench.py --full --steps 10 --warmup 2 > $OUT/bench.json 2> $OUT/bench.err
 rc=$?; echo "bench EXIT=$rc" >> $OUT/status; cat $OUT/bench.json; tail -3 $OUT/bench.err
 exit $rc

@@ -38,8 +38,8 @@ for s in "$@"; do
   case $s in
     probe) step probe 60 tools/bin/buffer_range_probe ;;
     tests_new) step tests_new 600 python3 -u -m pytest tests -m gpu -x -v -rP --timeout 300 --timeout-method thread -k "empty_rank or cold_solve_fresh or bench_gpus" ;;
-    bench_n4) step bench_n4 700 env KRCA_BENCH_BACKEND=gloo python3 bench.py --gpus 4 --steps 3 --warmup 1 --no-corr --cpu-runs 2 --cpu-warmup 1 ;;
-    bench_n2) step bench_n2 600 env KRCA_BENCH_BACKEND=gloo python3 bench.py --gpus 2 --steps 5 --warmup 2 ;;
+    bench_n4) step bench_n4 700 env KRCA_BENCH_BACKEND=gloo python3 bench.py --full --gpus 4 --steps 3 --warmup 1 --no-corr --cpu-runs 2 --cpu-warmup 1 ;;
+    bench_n2) step bench_n2 600 env KRCA_BENCH_BACKEND=gloo python3 bench.py --full --gpus 2 --steps 5 --warmup 2 ;;
     tests_logs) step tests_logs 600 python3 -u -m pytest tests -m gpu -x -v -rP --timeout 240 --timeout-method thread -k "log_scan or c2mini or c5 or stream or logs" ;;
     pprw_*) export KRCA_LIB=$PWD/kubernetes-rca-system_amd/lib/libkrca_${s#pprw_}.so; prof $s 300 tools/ppr_bench.py --reps 10; unset KRCA_LIB ;;
     pprbase) prof pprbase 300 tools/ppr_bench.py --reps 10 ;;
@@ -52,16 +52,16 @@ for s in "$@"; do
     tests) step tests 900 python3 -u -m pytest tests -m gpu -x -v -rP --timeout 240 --timeout-method thread ;;
     tests_corrq) step tests_corrq 600 python3 -u -m pytest tests/test_gpu_corr.py -x -v -rP --timeout 240 --timeout-method thread -k "batches or c3_every or full_vs" ;;
     tests_corr) step tests_corr 600 python3 -u -m pytest tests/test_gpu_corr.py -x -v -rP --timeout 240 --timeout-method thread ;;
-    bench) step bench 300 python3 bench.py ;;
+    bench) step bench 300 python3 bench.py --full ;;
     score_lds) step score_lds 300 python3 tools/score_ab.py --only pipe_c20,lds,lds_default_policy --rounds 3 --reps 5 ;;
     tests_score) step tests_score 300 python3 -u -m pytest tests/test_gpu_kernels.py -x -v -rP --timeout 120 --timeout-method thread -k "rolling_score" ;;
-    benchnt_*) v=${s#benchnt_}; export KRCA_PPR_NT=${v%%_*}; step $s 300 python3 bench.py --no-corr --no-cpu-baseline --no-verify; unset KRCA_PPR_NT ;;
-    benchx_*) v=${s#benchx_}; export KRCA_PPR_XCD=${v%%_*}; step $s 300 python3 bench.py --no-corr --no-cpu-baseline --no-verify --steps 20; unset KRCA_PPR_XCD ;;
+    benchnt_*) v=${s#benchnt_}; export KRCA_PPR_NT=${v%%_*}; step $s 300 python3 bench.py --full --no-corr --no-cpu-baseline --no-verify; unset KRCA_PPR_NT ;;
+    benchx_*) v=${s#benchx_}; export KRCA_PPR_XCD=${v%%_*}; step $s 300 python3 bench.py --full --no-corr --no-cpu-baseline --no-verify --steps 20; unset KRCA_PPR_XCD ;;
     benchhw_*) v=${s#benchhw_}; export GPU_MAX_HW_QUEUES=${v%%_*}; step $s 300 python3 bench.py --no-corr --no-cpu-baseline --no-verify --steps 20; unset GPU_MAX_HW_QUEUES ;;
-    benchq_*) export KRCA_PPR_GRID=${s#benchq_}; step $s 300 python3 bench.py --no-corr --no-cpu-baseline; unset KRCA_PPR_GRID ;;
+    benchq_*) export KRCA_PPR_GRID=${s#benchq_}; step $s 300 python3 bench.py --full --no-corr --no-cpu-baseline; unset KRCA_PPR_GRID ;;
     smoke) step smoke 300 python3 -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench_trace) prof bench_trace 400 bench.py --steps 10 --warmup 2 --no-cpu-baseline ;;
-    bench_trace_full) prof bench_trace_full 700 bench.py ;;
+    bench_trace) prof bench_trace 400 bench.py --full --steps 10 --warmup 2 --no-cpu-baseline ;;
+    bench_trace_full) prof bench_trace_full 700 bench.py --full ;;
     corr100k) prof corr100k 300 tools/prof_kernels.py corr --pods 100000 --reps 3 --tau 0.5 ;;
     corr100k_w*) export KRCA_LIB=$PWD/kubernetes-rca-system_amd/lib/libkrca_${s#corr100k_}.so; prof $s 300 tools/prof_kernels.py corr --pods 100000 --reps 3 --tau 0.5; unset KRCA_LIB ;;
     corrg_*) v=${s#corrg_}; export KRCA_CORR_RS_GROUP=${v%%_*}; prof $s 300 tools/prof_kernels.py corr --pods 100000 --reps 3 --tau 0.5; unset KRCA_CORR_RS_GROUP ;;
@@ -94,8 +94,8 @@ for s in "$@"; do
     ppr_w*) export KRCA_LIB=$PWD/kubernetes-rca-system_amd/lib/libkrca_${s#ppr_}.so; prof $s 300 tools/prof_kernels.py ppr --reps 5; unset KRCA_LIB ;;
     ppr_prev) export KRCA_LIB=$PWD/kubernetes-rca-system_amd/lib/libkrca_prev.so; prof ppr_prev 300 tools/prof_kernels.py ppr --reps 5; unset KRCA_LIB ;;
     ppr_nt) export KRCA_PPR_NT=1; prof ppr_nt 300 tools/prof_kernels.py ppr --reps 5; unset KRCA_PPR_NT ;;
-    bench_nograph) export KRCA_RCA_GRAPH=0; step bench_nograph 300 python3 bench.py --no-cpu-baseline; unset KRCA_RCA_GRAPH ;;
-    bench2) step bench2 300 python3 bench.py --no-cpu-baseline ;;
+    bench_nograph) export KRCA_RCA_GRAPH=0; step bench_nograph 300 python3 bench.py --full --no-cpu-baseline; unset KRCA_RCA_GRAPH ;;
+    bench2) step bench2 300 python3 bench.py --full --no-cpu-baseline ;;
     tests_tmpl) step tests_tmpl 600 python3 -u -m pytest tests -m gpu -x -v -rP --timeout 240 --timeout-method thread -k "template or tmpl or c2mini or c5 or stream" ;;
     logs) prof logs 300 tools/prof_kernels.py logs --reps 5 ;;
     logs_w*) export KRCA_LIB=$PWD/kubernetes-rca-system_amd/lib/libkrca_${s#logs_}.so; prof $s 300 tools/prof_kernels.py logs --reps 5; unset KRCA_LIB ;;

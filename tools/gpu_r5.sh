@@ -39,16 +39,16 @@ for s in "$@"; do
     tests) step tests 900 python3 -u -m pytest tests -m gpu -x -v -rP --timeout 300 --timeout-method thread ;;
     testsall_*) step $s 900 python3 -u -m pytest tests -m gpu -v -rP --timeout 300 --timeout-method thread -k "${s#testsall_}" ;;
     tests_*) step $s 900 python3 -u -m pytest tests -m gpu -x -v -rP --timeout 300 --timeout-method thread -k "${s#tests_}" ;;
-    bench) step bench 400 python3 bench.py ;;
-    benchgraph_*) step $s 400 env KRCA_RCA_GRAPH=1 DEBUG_CLR_GRAPH_PACKET_CAPTURE=0 python3 bench.py --no-corr --no-cpu-baseline ;;
-    bencheager_*) step $s 400 python3 bench.py --no-corr --no-cpu-baseline ;;
-    bench8gloo) step bench8gloo 900 env KRCA_BENCH_BACKEND=gloo python3 bench.py --gpus 8 --steps 3 --warmup 1 --no-corr --no-cpu-baseline ;;
-    bench8gloobal) step bench8gloobal 900 env KRCA_BENCH_BACKEND=gloo python3 bench.py --gpus 8 --steps 3 --warmup 1 --no-corr --no-cpu-baseline --ppr-partition balanced ;;
+    bench) step bench 400 python3 bench.py --full ;;
+    benchgraph_*) step $s 400 env KRCA_RCA_GRAPH=1 DEBUG_CLR_GRAPH_PACKET_CAPTURE=0 python3 bench.py --full --no-corr --no-cpu-baseline ;;
+    bencheager_*) step $s 400 python3 bench.py --full --no-corr --no-cpu-baseline ;;
+    bench8gloo) step bench8gloo 900 env KRCA_BENCH_BACKEND=gloo python3 bench.py --full --gpus 8 --steps 3 --warmup 1 --no-corr --no-cpu-baseline ;;
+    bench8gloobal) step bench8gloobal 900 env KRCA_BENCH_BACKEND=gloo python3 bench.py --full --gpus 8 --steps 3 --warmup 1 --no-corr --no-cpu-baseline --ppr-partition balanced ;;
     smoke) step smoke 300 python3 -c "import __graft_entry__ as g; g.smoke()" ;;
     graphdbg) step testsall_graphdbg 300 python3 -u -m pytest tests -m gpu -v -rP --timeout 120 --timeout-method thread -k "replay_after" &&
               step testsall_graphdbg_nopkt 300 env DEBUG_CLR_GRAPH_PACKET_CAPTURE=0 python3 -u -m pytest tests -m gpu -v -rP --timeout 120 --timeout-method thread -k "replay_after" ;;
-    bench_cpufull) step bench_cpufull 500 python3 bench.py --steps 3 --warmup 1 --cpu-full-mesh --no-corr ;;
-    bench_trace) prof bench_trace 500 bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-verify ;;
+    bench_cpufull) step bench_cpufull 500 python3 bench.py --full --steps 3 --warmup 1 --cpu-full-mesh --no-corr ;;
+    bench_trace) prof bench_trace 500 bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --no-verify ;;
     rank_def) step rank_def 900 python3 -u tools/ranking_ablation_c4.py --out $O/ranking_ablation_c4.json ;;
     rank_spread) step rank_spread 900 python3 -u tools/ranking_ablation_c4.py --spread --out $O/ranking_ablation_spread_c4.json ;;
     ppr) prof ppr 300 tools/ppr_bench.py --reps 10 ;;
