@@ -47,7 +47,7 @@ int krca_device_count(int* n_host);
 /* Kernel-development A/B switches: KRCA_SCORE_IMPL, KRCA_SCORE_CHUNK, KRCA_SCORE_NT, KRCA_PPR_GRID, KRCA_PPR_DICT,
  * KRCA_LOG_IMPL, KRCA_GROUP_IMPL, KRCA_CORR_DEBUG, KRCA_CORR_RS_GRID, KRCA_CORR_BATCH, KRCA_CORR_AMB_TILE,
  * KRCA_PPR_FUSE, KRCA_PPR_NT, KRCA_PPR_XCD, KRCA_LOG_FUSED, KRCA_CORR_RS_GROUP, KRCA_CORR_SIDE, KRCA_CORR_RS_Q16,
- * KRCA_CORR_CAPC, KRCA_CORR_KM_EXTRA, KRCA_CORR_RSG_GRID, KRCA_CORR_PROJ, KRCA_CORR_PERSIST.  Initialised once from the environment variables
+ * KRCA_CORR_CAPC, KRCA_CORR_KM_EXTRA, KRCA_CORR_RSG_GRID, KRCA_CORR_PROJ, KRCA_CORR_PERSIST, KRCA_TRACE_IMPL.  Initialised once from the environment variables
  * of the same names when the library loads; launchers never call getenv.  Process-global, not
  * thread-safe (set them before launching work).  Unknown names: KRCA_EINVAL. */
 int krca_tune_set(const char* name, int32_t value);
@@ -413,6 +413,56 @@ int krca_pod_classify(const uint8_t* pod_code, const int64_t* cont_off, const ui
 int32_t krca_group_max_rank(void);
 int krca_group_reduce(const int32_t* slot, const int64_t* key, int64_t N, int64_t n_ranked, int32_t S, int32_t R,
                       int64_t* rec, void* stream);
+
+/* ---- t1: trace analytics from columnar spans.  The reference's TracesAgent emits canned findings
+ * (ref:agents/traces_agent.py:209-381); the schemas computed here are the ones its data-access layer
+ * serves (ref:utils/mock_k8s_client.py:1146-1311: get_service_latency_stats {p50, p90, p95, p99, count},
+ * get_error_rate_by_service, get_service_dependencies, find_slow_operations).  One entry per span
+ * (krca/tracecols.py): svc in [0, S), parent = index of the parent span in the table (-1 = root or
+ * outside the window), dur_us, err (0 / 1).  All outputs are integers and bit-exact (integer add / max /
+ * or only); N < 2^31.
+ *
+ * Buckets: log-linear, 32 per octave, krca_trace_nbuckets() = 896.  d < 64: b = d.  Otherwise
+ * e = floor(log2 d), m = d >> (e-5) in [32, 63], b = 64 + (e-6)*32 + (m-32), lo(b) = m << (e-5),
+ * hi(b) = ((m+1) << (e-5)) - 1: lo <= d <= hi, hi - lo < lo/32, hi(895) = 2^32 - 1.  The three bucket
+ * helpers and krca_trace_lds_max_slots() are host functions without device work.
+ *
+ * krca_trace_link: a span is BAD if svc is outside [0, S): caller_svc = -1, self_us = 0, flags = 0, it
+ *   contributes to nothing and is counted in the first int64 of ws.  A parent is VALID if
+ *   0 <= parent[i] < N, parent[i] != i and the parent span is not bad; anything else is read as -1.
+ *   caller_svc[i] = svc[parent[i]] if the parent is valid and its service differs from svc[i], else -1
+ *   (a child span inside the same service is not a call);
+ *   self_us[i] = max(dur_us[i] - sum of dur_us over the valid children, 0), summed in 64 bits;
+ *   flags bit 0 = err, bit 1 = origin (errs and no valid child errs), bit 2 = propagated (errs, the
+ *   valid parent errs and caller_svc >= 0).  ws: krca_trace_link_ws_size(N) bytes, zeroed by the call.
+ * krca_trace_edges: the distinct keys caller*S + callee of the spans with caller_svc in [0, S) (and svc
+ *   in [0, S)), ASCENDING in edge_key[0 .. *n_edges_host); edge_slot[i] = rank of span i's key or -1.
+ *   SYNCHRONOUS (the distinct keys are ordered on the host inside the call).  If *n_edges_host > cap the
+ *   value is a lower bound and edge_key / edge_slot are undefined: grow cap and call again (as
+ *   krca_log_scan's line_cap).  ws: krca_trace_edge_ws_size(cap) bytes.
+ * krca_trace_stats: records (slot, val, flags); slots outside [0, S) are ignored.
+ *   rec[s] = {n, sum val, max val, n with bit 0, n with bit 1, n with bit 2, 0, 0}, hist[s][bucket(val)] += 1.
+ *   accumulate == 0: outputs zeroed first; != 0: added into what is there (max for word 2), so windows
+ *   or shards merge exactly.  S <= krca_trace_lds_max_slots(): LDS tables per workgroup; above: global
+ *   atomics behind a per-wave fold and a per-workgroup LDS cache of the records (KRCA_TRACE_IMPL: 0 by
+ *   size, 1 LDS, 2 folded + cached, 3 one atomic set per lane).  hist must be 8-byte aligned.
+ * krca_trace_quantiles: nearest rank, k = (q*n + 999) / 1000 for q = permille_host[j] in [1, 1000],
+ *   b* = first bucket whose cumulative count reaches k, out[s][j] = min(hi(b*), rec max), 0 where n = 0:
+ *   never below the true quantile and less than 1/32 above it.  Q <= 16. */
+int32_t krca_trace_nbuckets(void);
+int32_t krca_trace_bucket(uint32_t d);
+int krca_trace_bucket_bounds(int32_t b, uint32_t* lo_host, uint32_t* hi_host);
+int32_t krca_trace_lds_max_slots(void);
+int64_t krca_trace_link_ws_size(int64_t N);
+int krca_trace_link(const int32_t* svc, const int32_t* parent, const uint32_t* dur_us, const uint8_t* err, int64_t N,
+                    int32_t S, int32_t* caller_svc, uint32_t* self_us, uint8_t* flags, void* ws, void* stream);
+int64_t krca_trace_edge_ws_size(int64_t cap);
+int krca_trace_edges(const int32_t* caller_svc, const int32_t* svc, int64_t N, int32_t S, int64_t cap, void* ws,
+                     int64_t* edge_key, int32_t* edge_slot, int64_t* n_edges_host, void* stream);
+int krca_trace_stats(const int32_t* slot, const uint32_t* val, const uint8_t* flags, int64_t N, int32_t S,
+                     int32_t accumulate, int64_t* rec, uint32_t* hist, void* stream);
+int krca_trace_quantiles(const int64_t* rec, const uint32_t* hist, int32_t S, const int32_t* permille_host, int32_t Q,
+                         uint32_t* out, void* stream);
 
 #ifdef __cplusplus
 }

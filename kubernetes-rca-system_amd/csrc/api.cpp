@@ -43,6 +43,7 @@ const NamedKnob kKnobs[] = {
     {"KRCA_CORR_RSG_GRID", &Tuning::corr_rsg_grid},
     {"KRCA_CORR_PROJ", &Tuning::corr_proj},
     {"KRCA_CORR_PERSIST", &Tuning::corr_persist},
+    {"KRCA_TRACE_IMPL", &Tuning::trace_impl},
 };
 Tuning g_tune = {env_int("KRCA_SCORE_IMPL", 0), env_int("KRCA_SCORE_CHUNK", 20), env_int("KRCA_SCORE_NT", 1),
                  env_int("KRCA_PPR_GRID", 0),   env_int("KRCA_PPR_DICT", 1),     env_int("KRCA_LOG_IMPL", 0),
@@ -54,7 +55,7 @@ Tuning g_tune = {env_int("KRCA_SCORE_IMPL", 0), env_int("KRCA_SCORE_CHUNK", 20),
                  env_int("KRCA_CORR_SIDE", 0), env_int("KRCA_CORR_RS_Q16", 1),
                  env_int("KRCA_CORR_CAPC", 0), env_int("KRCA_CORR_KM_EXTRA", 6),
                  env_int("KRCA_CORR_RSG_GRID", 0), env_int("KRCA_CORR_PROJ", 2),
-                 env_int("KRCA_CORR_PERSIST", 0)};
+                 env_int("KRCA_CORR_PERSIST", 0), env_int("KRCA_TRACE_IMPL", 0)};
 const NamedKnob* find_knob(const char* name) {
   if (!name) return nullptr;
   for (const NamedKnob& k : kKnobs)

@@ -122,6 +122,8 @@ struct Tuning {
   int corr_persist;   // KRCA_CORR_PERSIST: the main pass as persistent workgroups that load the next tile's first
                       // K stage under the current one (1) or one workgroup per tile (0, default: R7a, the
                       // persistent form ran 2-5 % slower); same bits
+  int trace_impl;     // KRCA_TRACE_IMPL: krca_trace_stats path: 0 by size, 1 LDS tables per workgroup, 2 global
+                      // atomics behind the per-wave fold and the LDS record cache, 3 global atomics, one set per lane; same bits
 };
 const Tuning& tuning();
 int tuning_ppr_dict();

@@ -1,9 +1,14 @@
 """TracesAgent (host): tracing-platform detection and the reference's simulated findings.
 
 Reference: ref:agents/traces_agent.py:3-381 — no data arithmetic (its latency/error/dependency
-findings are canned, :209-381).  Out of the hot-path scope; kept so the comprehensive run
-correlates identical finding lists.
+findings are canned, :209-381); kept so the comprehensive run correlates identical finding lists.
+
+A client that serves spans (``get_span_columns(namespace)`` -> krca.tracecols.SpanColumns, or
+``get_trace_details`` spans with ``parentId``) takes the data path instead: the same analyses in the
+same order, computed on the device by ``engine.trace_analyze`` (krca/tracecols.py), plus the additive
+``trace_stats`` key.
 """
+from .. import tracecols
 from .base import BaseAgent
 
 _TRACE_KEYS = ('jaeger', 'zipkin', 'tracing', 'otel', 'opentelemetry')
@@ -14,6 +19,9 @@ class TracesAgent(BaseAgent):
         self.reset()
         try:
             self._maybe_set_context(context)
+            cols = self._span_columns(namespace)
+            if cols is not None:
+                return self._measured(namespace, cols)
             found = {p: self._platform(p) for p in ('jaeger', 'zipkin', 'opentelemetry')}
             if not any(found.values()):
                 self.add_reasoning_step(observation="No distributed tracing platform detected in the cluster",
@@ -41,6 +49,38 @@ class TracesAgent(BaseAgent):
             return self.get_results()
         except Exception as e:
             return self._error_result("traces", e)
+
+    # -- the data path: analyses computed from spans (krca/tracecols.py, csrc/trace.hip) ------
+    def _span_columns(self, namespace):
+        """SpanColumns from the bulk accessor ``get_span_columns(namespace)``, or from
+        ``get_trace_ids`` / ``get_trace_details`` when their spans are plain and carry ``parentId``;
+        None otherwise (the canned path below, unchanged)."""
+        bulk = getattr(self.k8s_client, 'get_span_columns', None)
+        if bulk is not None:
+            cols = bulk(namespace)
+            if cols is not None:
+                return cols
+        ids, details = (getattr(self.k8s_client, n, None) for n in ('get_trace_ids', 'get_trace_details'))
+        if ids is None or details is None:
+            return None
+        try:
+            cols = tracecols.encode_spans([details(t) for t in ids()])
+        except Exception:
+            return None
+        return cols if cols is not None and cols.has_parents and len(cols) else None
+
+    def _measured(self, namespace, cols):
+        self.add_reasoning_step(
+            observation=f"Found {len(cols)} spans of {len(cols.services)} services in namespace {namespace}",
+            conclusion="Will analyze the recorded trace data")
+        if len(cols) == 0:
+            return self.get_results()
+        stats = self.engine.trace_analyze(cols)
+        for kind, kw in tracecols.analyze(stats):
+            (self.add_finding if kind == 'finding' else self.add_reasoning_step)(**kw)
+        res = self.get_results()
+        res["trace_stats"] = stats.summary()  # additive key (SURVEY.md §8b)
+        return res
 
     def _platform(self, name):  # ref :118-146
         try:

@@ -107,6 +107,16 @@ SIGNATURES = {
     "krca_topk_workspace_size": (c_i64, [c_i64, c_i32]),
     "krca_topk_f32": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp]),
     "krca_topk_i64": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    "krca_trace_nbuckets": (c_i32, []),
+    "krca_trace_bucket": (c_i32, [ctypes.c_uint32]),
+    "krca_trace_bucket_bounds": (c_i32, [c_i32, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]),
+    "krca_trace_lds_max_slots": (c_i32, []),
+    "krca_trace_link_ws_size": (c_i64, [c_i64]),
+    "krca_trace_link": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "krca_trace_edge_ws_size": (c_i64, [c_i64]),
+    "krca_trace_edges": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_i64, c_vp, c_vp, c_vp, ctypes.POINTER(c_i64), c_vp]),
+    "krca_trace_stats": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    "krca_trace_quantiles": (c_i32, [c_vp, c_vp, c_i32, ctypes.POINTER(c_i32), c_i32, c_vp, c_vp]),
 }
 
 KRCA_ENOTCONV = -70
@@ -429,6 +439,126 @@ class NativeEngine:
         rec = self.group_reduce_device(self._dev(slot), self._dev(key), S, R, n_ranked).cpu().numpy()
         return (rec[:, 0].astype(np.int32), (rec[:, 1] >> 32).astype(np.int32),
                 (rec[:, 1] & 0xFFFFFFFF).astype(np.int32), np.ascontiguousarray(rec[:, 2:2 + R].T))
+
+    # -- t1: trace analytics (include/krca.h, csrc/trace.hip) -----------------------------------
+    # uint32 columns travel as int32 tensors (same bits); host results are viewed back as uint32
+    def _dev_n(self, a, np_dtype):
+        """Host or device array -> contiguous device tensor with at least one element."""
+        torch = self.torch
+        if isinstance(a, torch.Tensor):
+            return a.to(self.device).contiguous() if a.numel() else torch.zeros(1, dtype=a.dtype, device=self.device)
+        a = np.ascontiguousarray(a, np_dtype)
+        if a.dtype == np.uint32:
+            a = a.view(np.int32)
+        return self._dev(a if len(a) else np.zeros(1, a.dtype))
+
+    def trace_link_device(self, svc, parent, dur, err, N, S):
+        """-> (caller_svc int32, self_us int32 (uint32 bits), flags uint8, ws) device tensors; ws's
+        first int64 is the number of bad spans once the stream has run."""
+        torch = self.torch
+        n1 = max(int(N), 1)
+        caller = torch.empty(n1, dtype=torch.int32, device=self.device)
+        self_us = torch.empty(n1, dtype=torch.int32, device=self.device)
+        flags = torch.empty(n1, dtype=torch.uint8, device=self.device)
+        ws = torch.empty(int(self.lib.krca_trace_link_ws_size(N)) // 8, dtype=torch.int64, device=self.device)
+        _check(self.lib.krca_trace_link(self.ptr(svc), self.ptr(parent), self.ptr(dur), self.ptr(err), int(N), int(S),
+                                        self.ptr(caller), self.ptr(self_us), self.ptr(flags), self.ptr(ws),
+                                        self._stream()), "krca_trace_link")
+        return caller, self_us, flags, ws
+
+    def trace_link(self, svc, parent, dur_us, err, S):
+        """Host arrays -> (caller_svc int32[N], self_us uint32[N], flags uint8[N], n_bad)."""
+        N = len(svc)
+        c, s, f, ws = self.trace_link_device(self._dev_n(svc, np.int32), self._dev_n(parent, np.int32),
+                                             self._dev_n(dur_us, np.uint32), self._dev_n(err, np.uint8), N, S)
+        return c[:N].cpu().numpy(), s[:N].cpu().numpy().view(np.uint32), f[:N].cpu().numpy(), int(ws[0].item())
+
+    def trace_edges_device(self, caller, svc, N, S, cap=None):
+        """-> (edge_key int64[E] ascending, edge_slot int32[max(N, 1)], E) device tensors; with cap
+        given, one call: E > cap means the outputs are invalid (returned as None)."""
+        torch = self.torch
+        grow = cap is None
+        cap = int(getattr(self, "_edge_cap", 4096) if grow else cap)
+        slot = torch.empty(max(int(N), 1), dtype=torch.int32, device=self.device)
+        while True:
+            ws = self._workspace("trace_edges", self.lib.krca_trace_edge_ws_size(cap))
+            key = torch.empty(max(cap, 1), dtype=torch.int64, device=self.device)
+            ne = c_i64(0)
+            _check(self.lib.krca_trace_edges(self.ptr(caller), self.ptr(svc), int(N), int(S), cap, self.ptr(ws),
+                                             self.ptr(key), self.ptr(slot), ctypes.byref(ne), self._stream()),
+                   "krca_trace_edges")
+            E = int(ne.value)
+            if E <= cap:
+                return key[:E], slot, E
+            if not grow:
+                return None, None, E
+            cap = max(2 * cap, E + E // 4)
+            self._edge_cap = cap
+
+    def trace_edges(self, caller_svc, svc, S, cap=None):
+        """Host arrays -> (edge_key int64[E], edge_slot int32[N], E); (None, None, E) if E > cap."""
+        N = len(svc)
+        k, s, E = self.trace_edges_device(self._dev_n(caller_svc, np.int32), self._dev_n(svc, np.int32), N, S, cap)
+        if k is None:
+            return None, None, E
+        return k.cpu().numpy(), s[:N].cpu().numpy(), E
+
+    def trace_stats_device(self, slot, val, flags, N, S, accumulate=False, rec=None, hist=None):
+        """-> (rec int64 [S, 8], hist int32 [S, NB] (uint32 bits)) device tensors."""
+        torch = self.torch
+        nb = int(self.lib.krca_trace_nbuckets())
+        if rec is None:
+            rec = torch.empty((max(int(S), 1), 8), dtype=torch.int64, device=self.device)
+            hist = torch.empty((max(int(S), 1), nb), dtype=torch.int32, device=self.device)
+            if accumulate:
+                rec.zero_()
+                hist.zero_()
+        _check(self.lib.krca_trace_stats(self.ptr(slot), self.ptr(val), self.ptr(flags), int(N), int(S),
+                                         int(bool(accumulate)), self.ptr(rec), self.ptr(hist), self._stream()),
+               "krca_trace_stats")
+        return rec, hist
+
+    def trace_quantiles_device(self, rec, hist, S, permille):
+        torch = self.torch
+        q = (c_i32 * len(permille))(*[int(p) for p in permille])
+        out = torch.empty((max(int(S), 1), len(permille)), dtype=torch.int32, device=self.device)
+        _check(self.lib.krca_trace_quantiles(self.ptr(rec), self.ptr(hist), int(S), q, len(permille), self.ptr(out),
+                                             self._stream()), "krca_trace_quantiles")
+        return out
+
+    def trace_stats(self, slot, val, flags, S, permille=(500, 900, 950, 990), accumulate=False, prev=None):
+        """Host arrays -> (rec int64[S, 8], hist uint32[S, NB], q uint32[S, Q]); prev = (rec, hist)
+        host arrays to add into (accumulate)."""
+        N = len(slot)
+        rec = hist = None
+        if prev is not None:
+            rec = self._dev(np.ascontiguousarray(prev[0], np.int64))
+            hist = self._dev(np.ascontiguousarray(prev[1], np.uint32).view(np.int32))
+        rec, hist = self.trace_stats_device(self._dev_n(slot, np.int32), self._dev_n(val, np.uint32),
+                                            self._dev_n(flags, np.uint8), N, S, accumulate, rec, hist)
+        q = self.trace_quantiles_device(rec, hist, S, permille)
+        return rec[:S].cpu().numpy(), hist[:S].cpu().numpy().view(np.uint32), q[:S].cpu().numpy().view(np.uint32)
+
+    def trace_analyze(self, cols):
+        """SpanColumns -> tracecols.TraceStats: link, edges, then per service (duration and self
+        time), per call edge and per operation: records + 500 / 900 / 950 / 990 permille."""
+        from . import tracecols
+        torch = self.torch
+        N, S, n_ops = len(cols), len(cols.services), len(cols.ops)
+        svc, parent = self._dev_n(cols.svc, np.int32), self._dev_n(cols.parent, np.int32)
+        dur, err, op = self._dev_n(cols.dur_us, np.uint32), self._dev_n(cols.err, np.uint8), self._dev_n(cols.op, np.int32)
+        caller, self_us, flags, ws = self.trace_link_device(svc, parent, dur, err, N, S)
+        edge_key, edge_slot, E = self.trace_edges_device(caller, svc, N, S)  # synchronises
+        n_bad = int(ws[0].item())
+        if n_bad:  # a bad span contributes to nothing: keep it out of its operation's slot too
+            op = torch.where((svc >= 0) & (svc < S), op, torch.full_like(op, -1))
+        out = {}
+        for name, slot, val, n_slots in (("svc", svc, dur, S), ("self", svc, self_us, S), ("edge", edge_slot, dur, E),
+                                         ("op", op, dur, n_ops)):
+            rec, hist = self.trace_stats_device(slot, val, flags, N, n_slots)
+            q = self.trace_quantiles_device(rec, hist, n_slots, tracecols.PERMILLE)
+            out[name] = (rec[:n_slots].cpu().numpy(), q[:n_slots].cpu().numpy().view(np.uint32))
+        return tracecols.TraceStats(cols.services, cols.ops, N, n_bad, edge_key.cpu().numpy(), out)
 
     # -- top-k -------------------------------------------------------------------------------
     def topk_device(self, v, k):
