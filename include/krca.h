@@ -83,6 +83,56 @@ int krca_rolling_score(const float* x, int64_t P, int32_t M, int32_t T, int32_t 
 #define KRCA_SCORE_LDS 5 /* A/B (KRCA_SCORE_IMPL=5, W = 60): rows staged by LDS-DMA, 1 KiB per wave instruction */
 int krca_rolling_score_variant(int64_t P, int32_t M, int32_t T, int32_t W);
 
+/* ---- a5t: anomaly timeline -- WHEN each pod went bad (new primitive; plugs in at
+ * ref:agents/metrics_agent.py:44-47 beside krca_rolling_score).  One pass over x; z_last, score,
+ * n_exceed and flags are bit-identical to krca_rolling_score on the same input.  Episodes, per
+ * series s = p*M + m, over exceed(t) above for t in [W, T), with gap tolerance gap >= 0 and minimum
+ * count min_count >= 1:
+ *   an episode is a maximal run of exceedance steps with consecutive exceedances at most `gap`
+ *   steps apart (t - last <= gap continues it, t - last > gap starts a new one); it records its
+ *   first step (onset), its last step, its number of exceedances (cnt) and
+ *   peak = max over its exceedances of (float)(fabs(A) / sqrt(B)) (float64, rounded to float32);
+ *   it is sustained when cnt >= min_count.  The series keeps its sustained episode of the largest
+ *   peak (the later one on equal peaks), or none.
+ * Per pod, over its M series: the anchor is the series whose kept episode has the largest peak
+ * (ties: lowest m); members are the series with a kept episode such that onset_m <= last_a + gap
+ * and onset_a <= last_m + gap.   Outputs:
+ *   onset[p] = min of the members' onsets,   last[p] = max of their last steps,
+ *   count[p] = sum of their cnt,   peak[p] = the anchor's peak,
+ *   lead[p] = the member with the smallest onset (ties: lowest m),   n_metrics[p] = members.
+ * A pod with no kept episode (always when T <= W): onset = last = -1, count = 0, peak = 0,
+ * lead = -1, n_metrics = 0.  A NaN sample never exceeds.  The software-pipelined kernels run
+ * wherever krca_rolling_score runs them (KRCA_SCORE_PIPE / KRCA_SCORE_PIPE_ROWS), the re-reading
+ * form everywhere else. */
+int krca_rolling_timeline(const float* x, int64_t P, int32_t M, int32_t T, int32_t W, float z_thr,
+                          int32_t gap, int32_t min_count,
+                          float* z_last, float* score, int32_t* n_exceed, uint8_t* flags, /* as krca_rolling_score */
+                          int32_t* onset /*[P]*/, int32_t* last /*[P]*/, int32_t* count /*[P]*/, float* peak /*[P]*/,
+                          int8_t* lead /*[P]*/, uint8_t* n_metrics /*[P]*/, void* stream);
+
+/* Onset precedence over the pull-CSR (row k = the callers j of k, edges j -> k), single device, whole
+ * graph; onset as krca_rolling_timeline writes it (< 0: none).  An edge j -> k with j != k,
+ * onset_j >= 0 and onset_k >= 0 is classified, with slack >= 0:  k EARLIER than j when
+ * onset_k + slack < onset_j,  k LATER when onset_j + slack < onset_k,  CONCURRENT otherwise.
+ * Per caller j, over the rows j appears in: dep_earlier[j], dep_concurrent[j] = its earlier /
+ * concurrent dependencies, dep_first[j] = min of ((int64)onset_k << 32) | k over its earlier
+ * dependencies (INT64_MAX: none).  Per callee k: caller_later[k] (callers k is earlier than),
+ * caller_concurrent[k], caller_earlier[k] (callers k is later than).  Pods with onset < 0 get zeros
+ * and INT64_MAX.  Only the rows of pods with an onset are walked; integer counts and an integer min:
+ * independent of the schedule.  ws: krca_rca_precede_ws_size(N) bytes, no initialisation needed;
+ * every output is [N] and fully written.  Not for graph capture (memsets).
+ * krca_rca_first_mover_key: a pod with onset >= 0 and dep_earlier == 0 is a first mover;
+ * key = (min(caller_later + caller_concurrent, 2^20 - 1) << 32) | float bits of peak (peak >= 0:
+ * monotone) for a first mover, 0 for every other pod; feed it to krca_topk_i64. */
+int64_t krca_rca_precede_ws_size(int64_t N);
+int krca_rca_precede(const int32_t* onset, int64_t N, int32_t slack, const int64_t* row_ptr, const int32_t* col,
+                     int32_t* dep_earlier, int32_t* dep_concurrent, int64_t* dep_first,
+                     int32_t* caller_later, int32_t* caller_concurrent, int32_t* caller_earlier,
+                     void* ws, void* stream);
+int krca_rca_first_mover_key(const int32_t* onset, const float* peak, const int32_t* dep_earlier,
+                             const int32_t* caller_later, const int32_t* caller_concurrent, int64_t N,
+                             int64_t* key, void* stream);
+
 /* ---- a11/a12: 13-category log histograms (ref:agents/logs_agent.py:124-181) ----------------
  * text = UTF-8 bytes of D container logs, container d = text[doc_off[d], doc_off[d+1]).
  * Contract: doc_off[0] == 0, doc_off[D] == nbytes, doc_off non-decreasing, each container valid

@@ -3,6 +3,8 @@
 //  krca_usage_flags    — the instantaneous CPU / memory thresholds of
 //                        ref:agents/metrics_agent.py:88-114 and :135-161 (x > 80 strict, high if > 90).
 //  krca_rolling_score  — rolling-window z-scores over a time-major [T][P][M] float32 tensor.
+//  krca_rolling_timeline — the same pass, also keeping WHEN each series exceeded: episodes of
+//                        exceedances in the exceed branch, combined per pod in the epilogue.
 //
 // Design (MI355X): HBM-streaming, one lane per series s = p*M + m.  At every time step a wave
 // reads 64 consecutive floats (256 B, fully coalesced) and the trailing window of W samples
@@ -55,6 +57,132 @@ __device__ __forceinline__ void step(StepState& st, float v, float old, double W
   }
   st.s1 = (st.s1 + vd) - od;
   st.s2 = fma(-od, od, fma(vd, vd, st.s2));
+}
+
+// The same step for the kernels that exist in a scoring and a timeline form.  `ep` sees the
+// exceedances only: NoEpisodes for krca_rolling_score (plain step(): the code of its kernels is what
+// it was without the parameter), Episodes for krca_rolling_timeline (step t of the series).
+struct NoEpisodes {
+  static constexpr bool kTrack = false;
+  struct Args {};
+  __device__ __forceinline__ explicit NoEpisodes(Args) {}
+};
+
+struct TimelineOut {
+  int32_t* onset;
+  int32_t* last;
+  int32_t* count;
+  float* peak;
+  int8_t* lead;
+  uint8_t* n_metrics;
+};
+
+template <class Ep>
+__device__ __forceinline__ void step(StepState& st, float v, float old, double Wd, double epsB, double thr2,
+                                     bool last, Ep& ep, int t) {
+  if constexpr (!Ep::kTrack) {
+    step(st, v, old, Wd, epsB, thr2, last);
+  } else {
+    const double vd = (double)v;
+    const double od = (double)old;
+    const double A = fma(Wd, vd, -st.s1);
+    const double B = fma(Wd, st.s2, -(st.s1 * st.s1));
+    const bool exceed = (B > epsB) && (fma(A, A, -(thr2 * B)) > 0.0);
+    st.cnt += exceed;
+    if (exceed) ep.hit(t, A, B);  // rare and divergent; the only place episode state is touched
+    if (last) {
+      st.al = A;
+      st.bl = B;
+    }
+    st.s1 = (st.s1 + vd) - od;
+    st.s2 = fma(-od, od, fma(vd, vd, st.s2));
+  }
+}
+
+// Episode state of one series (krca_rolling_timeline; semantics in include/krca.h): the open
+// episode (c_*) and the kept one (k_*) = the sustained episode (cnt >= min_count) of the largest
+// peak so far, the later one on equal peaks.  c_cnt == 0: none open; k_cnt == 0: none kept.
+struct Episodes {
+  static constexpr bool kTrack = true;
+  struct Args {
+    int gap, min_count;
+    TimelineOut out;
+  };
+  int gap, min_count;
+  int c_on, c_last, c_cnt;
+  float c_peak;
+  int k_on, k_last, k_cnt;
+  float k_peak;
+  __device__ __forceinline__ explicit Episodes(const Args& a)
+      : gap(a.gap), min_count(a.min_count), c_on(-1), c_last(-1), c_cnt(0), c_peak(0.f), k_on(-1), k_last(-1),
+        k_cnt(0), k_peak(-1.f) {}
+  // the open episode ended: keep it if it is sustained and at least as strong as the kept one
+  __device__ __forceinline__ void close() {
+    if (c_cnt >= min_count && c_peak >= k_peak) {
+      k_on = c_on;
+      k_last = c_last;
+      k_cnt = c_cnt;
+      k_peak = c_peak;
+    }
+  }
+  __device__ __forceinline__ void hit(int t, double A, double B) {
+    const float z = (float)(fabs(A) / sqrt(B));  // pod_epilogue's expression for z_last
+    if (c_cnt > 0 && t - c_last <= gap) {
+      c_last = t;
+      ++c_cnt;
+      c_peak = fmaxf(c_peak, z);
+    } else {
+      close();
+      c_on = c_last = t;
+      c_cnt = 1;
+      c_peak = z;
+    }
+  }
+};
+
+// Pod combine of the kept episodes, over the pod's M wave-aligned lanes (every lane of the wave
+// takes part in the shuffles; a lane past S contributes "no episode").  Anchor = the kept episode
+// of the largest peak (ties: lowest m); members = the kept episodes within `gap` of overlapping the
+// anchor's [onset, last].
+__device__ __forceinline__ void timeline_epilogue(Episodes& ep, int64_t s, bool active, int M,
+                                                  const TimelineOut& o) {
+  ep.close();
+  const bool has = active && ep.k_cnt > 0;
+  const int lane = threadIdx.x & 63;
+  const int m = lane & (M - 1);  // == s & (M - 1): workgroups start at a multiple of 256 series
+  float ap = has ? ep.k_peak : -1.f;
+  int am = m;
+  for (int off = 1; off < M; off <<= 1) {
+    const float op = __shfl_xor(ap, off, 64);
+    const int om = __shfl_xor(am, off, 64);
+    if (op > ap || (op == ap && om < am)) {
+      ap = op;
+      am = om;
+    }
+  }
+  const int src = (lane & ~(M - 1)) + am;
+  const int64_t a_on = __shfl(ep.k_on, src, 64), a_last = __shfl(ep.k_last, src, 64);
+  const bool mem = has && (int64_t)ep.k_on <= a_last + ep.gap && a_on <= (int64_t)ep.k_last + ep.gap;
+  long long first = mem ? (((long long)ep.k_on << 8) | m) : INT64_MAX;  // min: earliest onset, then lowest m
+  int lastv = mem ? ep.k_last : -1;
+  int cnt = mem ? ep.k_cnt : 0;
+  int nm = mem ? 1 : 0;
+  for (int off = 1; off < M; off <<= 1) {
+    const long long of = __shfl_xor(first, off, 64);
+    first = of < first ? of : first;
+    const int ol = __shfl_xor(lastv, off, 64);
+    lastv = ol > lastv ? ol : lastv;
+    cnt += __shfl_xor(cnt, off, 64);
+    nm += __shfl_xor(nm, off, 64);
+  }
+  if (!active || m != 0) return;
+  const int64_t p = s / M;
+  o.onset[p] = nm ? (int32_t)(first >> 8) : -1;
+  o.last[p] = lastv;
+  o.count[p] = cnt;
+  o.peak[p] = nm ? ap : 0.f;
+  o.lead[p] = nm ? (int8_t)(first & 0xff) : (int8_t)-1;
+  o.n_metrics[p] = (uint8_t)nm;
 }
 
 // Pod epilogue shared by both kernels: z_last per series, pod max|z|, exceedance sum, flags.
@@ -250,11 +378,13 @@ struct BlockRows {
   }
 };
 
-template <int W, int C, int AUX = 0, class Rows = SpanRows>
+// Ep = Episodes: krca_rolling_timeline's form of the same pass (the episode state in the exceed
+// branch, the pod combine of the kept episodes behind the scorer's epilogue).
+template <int W, int C, int AUX = 0, class Rows = SpanRows, class Ep = NoEpisodes>
 __global__ __launch_bounds__(256) void rolling_score_pipe(const float* __restrict__ x, int64_t S, int T, int M,
                                                           double thr2, float* __restrict__ z_last,
                                                           float* __restrict__ score, int32_t* __restrict__ n_exceed,
-                                                          uint8_t* __restrict__ flags) {
+                                                          uint8_t* __restrict__ flags, typename Ep::Args targs) {
   static_assert(W % C == 0, "chunk must divide the window");
   constexpr int NC = W / C;
   const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -262,6 +392,7 @@ __global__ __launch_bounds__(256) void rolling_score_pipe(const float* __restric
   const Rows rows(x, S, T, s, active);
   const double Wd = (double)W, epsB = kVarEps * Wd * Wd;
   StepState st{0.0, 0.0, 0, 0.0, 0.0};
+  Ep ep(targs);
   float ring[W];
   float cur[C];
   // prologue: rows [0, W) fill the window (requires T > W, checked by the launcher)
@@ -287,7 +418,7 @@ __global__ __launch_bounds__(256) void rolling_score_pipe(const float* __restric
       rows.template load<C, AUX>(t0 + (c + 1) * C, nxt);
 #pragma unroll
       for (int j = 0; j < C; ++j) {
-        step(st, cur[j], ring[c * C + j], Wd, epsB, thr2, false);
+        step(st, cur[j], ring[c * C + j], Wd, epsB, thr2, false, ep, t0 + c * C + j);
         ring[c * C + j] = cur[j];
       }
 #pragma unroll
@@ -302,12 +433,13 @@ __global__ __launch_bounds__(256) void rolling_score_pipe(const float* __restric
     for (int j = 0; j < C; ++j) {
       const int t = t0 + c * C + j;
       if (t < T) {
-        step(st, cur[j], ring[c * C + j], Wd, epsB, thr2, t == T - 1);
+        step(st, cur[j], ring[c * C + j], Wd, epsB, thr2, t == T - 1, ep, t);
         ring[c * C + j] = cur[j];
       }
     }
   }
   pod_epilogue(st, epsB, s, active, M, T, x + (active ? s : 0), S, z_last, score, n_exceed, flags);
+  if constexpr (Ep::kTrack) timeline_epilogue(ep, s, active, M, targs.out);
 }
 
 // LDS-DMA form of rolling_score_pipe (KRCA_SCORE_IMPL=5, A/B; same steps in the same order, same
@@ -397,16 +529,18 @@ __global__ __launch_bounds__(256) void rolling_score_lds(const float* __restrict
 }
 
 // Any W: the outgoing sample x[t-W] is re-read (same values, same arithmetic -> same bits).
+template <class Ep = NoEpisodes>
 __global__ __launch_bounds__(256) void rolling_score_reread(const float* __restrict__ x, int64_t S, int T, int W,
                                                             int M, double thr2, float* __restrict__ z_last,
                                                             float* __restrict__ score,
                                                             int32_t* __restrict__ n_exceed,
-                                                            uint8_t* __restrict__ flags) {
+                                                            uint8_t* __restrict__ flags, typename Ep::Args targs) {
   const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const bool active = s < S;
   const float* xs = x + (active ? s : 0);
   const double Wd = (double)W, epsB = kVarEps * Wd * Wd;
   StepState st{0.0, 0.0, 0, 0.0, 0.0};
+  Ep ep(targs);
   for (int j = 0; j < W && j < T; ++j) {
     const double vd = active ? (double)xs[(int64_t)j * S] : 0.0;
     st.s1 = st.s1 + vd;
@@ -415,9 +549,10 @@ __global__ __launch_bounds__(256) void rolling_score_reread(const float* __restr
   for (int t = W; t < T; ++t) {
     const float v = active ? xs[(int64_t)t * S] : 0.f;
     const float o = active ? xs[(int64_t)(t - W) * S] : 0.f;
-    step(st, v, o, Wd, epsB, thr2, t == T - 1);
+    step(st, v, o, Wd, epsB, thr2, t == T - 1, ep, t);
   }
   pod_epilogue(st, epsB, s, active, M, T, xs, S, z_last, score, n_exceed, flags);
+  if constexpr (Ep::kTrack) timeline_epilogue(ep, s, active, M, targs.out);
 }
 
 // ---- streaming rescoring (BASELINE configs[4]) ----------------------------
@@ -563,10 +698,10 @@ int krca_rolling_score(const float* x, int64_t P, int32_t M, int32_t T, int32_t 
 #define KRCA_PIPE_AS(WV, CV, ROWS)                                                                               \
   if (nt)                                                                                                        \
     hipLaunchKernelGGL((rolling_score_pipe<WV, CV, 2, ROWS>), grid, block, 0, st, x, S, T, M, thr2, z_last, score, \
-                       n_exceed, flags);                                                                         \
+                       n_exceed, flags, NoEpisodes::Args{});                                                     \
   else                                                                                                           \
     hipLaunchKernelGGL((rolling_score_pipe<WV, CV, 0, ROWS>), grid, block, 0, st, x, S, T, M, thr2, z_last, score, \
-                       n_exceed, flags);
+                       n_exceed, flags, NoEpisodes::Args{});
 #define KRCA_PIPE(WV, CV)                                    \
   if (variant == KRCA_SCORE_PIPE) { KRCA_PIPE_AS(WV, CV, SpanRows) } \
   else { KRCA_PIPE_AS(WV, CV, BlockRows) }
@@ -611,12 +746,60 @@ int krca_rolling_score(const float* x, int64_t P, int32_t M, int32_t T, int32_t 
       else { KRCA_RING(10) }
       break;
     default:
-      hipLaunchKernelGGL(rolling_score_reread, grid, block, 0, st, x, S, T, W, M, thr2, z_last, score, n_exceed,
-                         flags);
+      hipLaunchKernelGGL(rolling_score_reread<NoEpisodes>, grid, block, 0, st, x, S, T, W, M, thr2, z_last, score,
+                         n_exceed, flags, NoEpisodes::Args{});
   }
 #undef KRCA_PIPE
 #undef KRCA_PIPE_AS
 #undef KRCA_RING
+  KRCA_LAUNCH_CHECK();
+  return KRCA_OK;
+}
+
+int krca_rolling_timeline(const float* x, int64_t P, int32_t M, int32_t T, int32_t W, float z_thr, int32_t gap,
+                          int32_t min_count, float* z_last, float* score, int32_t* n_exceed, uint8_t* flags,
+                          int32_t* onset, int32_t* last, int32_t* count, float* peak, int8_t* lead,
+                          uint8_t* n_metrics, void* stream) {
+  KRCA_CHECK_ARG(P >= 0 && T >= 0 && W >= 1, "krca_rolling_timeline: bad sizes P=%lld T=%d W=%d", (long long)P, T, W);
+  KRCA_CHECK_ARG(M >= 1 && M <= 64 && (M & (M - 1)) == 0, "krca_rolling_timeline: M=%d must be a power of two <= 64",
+                 M);
+  KRCA_CHECK_ARG(gap >= 0 && min_count >= 1, "krca_rolling_timeline: gap=%d must be >= 0, min_count=%d >= 1", gap,
+                 min_count);
+  if (P == 0) return KRCA_OK;
+  KRCA_CHECK_ARG(x && z_last && score && n_exceed && flags && onset && last && count && peak && lead && n_metrics,
+                 "krca_rolling_timeline: null pointer");
+  const int64_t S = P * (int64_t)M;
+  KRCA_CHECK_ARG(S < (int64_t(1) << 32), "krca_rolling_timeline: P*M must be < 2^32");
+  const double thr2 = (double)z_thr * (double)z_thr;
+  const dim3 grid((unsigned)krca::ceil_div(S, 256)), block(256);
+  hipStream_t st = krca::as_stream(stream);
+  const bool nt = krca::tuning().score_nt != 0;
+  const Episodes::Args tl{gap, min_count, TimelineOut{onset, last, count, peak, lead, n_metrics}};
+  // the pipelined kernel wherever krca_rolling_score runs one (one chunk size per window: the W = 60
+  // chunk knob is the scorer's A/B), the re-reading form everywhere else (any W, T <= W, forced A/B
+  // variants)
+  const int variant = krca_rolling_score_variant(P, M, T, W);
+  const bool pipe = variant == KRCA_SCORE_PIPE || variant == KRCA_SCORE_PIPE_ROWS;
+  const int chunk = W == 60 ? 20 : (W == 30 ? 15 : (W == 20 ? 10 : W));
+  const bool span = variant == KRCA_SCORE_PIPE && S * 4 * chunk < (int64_t(1) << 31);
+#define KRCA_TL_AS(WV, CV, AUXV, ROWS)                                                                          \
+  hipLaunchKernelGGL((rolling_score_pipe<WV, CV, AUXV, ROWS, Episodes>), grid, block, 0, st, x, S, T, M, thr2, \
+                     z_last, score, n_exceed, flags, tl)
+#define KRCA_TL(WV, CV)                                  \
+  if (span && nt) KRCA_TL_AS(WV, CV, 2, SpanRows);       \
+  else if (span) KRCA_TL_AS(WV, CV, 0, SpanRows);        \
+  else if (nt) KRCA_TL_AS(WV, CV, 2, BlockRows);         \
+  else KRCA_TL_AS(WV, CV, 0, BlockRows)
+  if (pipe && W == 60) { KRCA_TL(60, 20); }
+  else if (pipe && W == 30) { KRCA_TL(30, 15); }
+  else if (pipe && W == 20) { KRCA_TL(20, 10); }
+  else if (pipe && W == 15) { KRCA_TL(15, 15); }
+  else if (pipe && W == 10) { KRCA_TL(10, 10); }
+  else
+    hipLaunchKernelGGL(rolling_score_reread<Episodes>, grid, block, 0, st, x, S, T, W, M, thr2, z_last, score, n_exceed,
+                       flags, tl);
+#undef KRCA_TL
+#undef KRCA_TL_AS
   KRCA_LAUNCH_CHECK();
   return KRCA_OK;
 }

@@ -38,11 +38,17 @@ def to_f32_threshold_safe(values):
 
 
 class MetricsAgent(BaseAgent):
-    def __init__(self, k8s_client, engine=None, window=60, z_threshold=3.0, anomaly_topk=10):
+    def __init__(self, k8s_client, engine=None, window=60, z_threshold=3.0, anomaly_topk=10, timeline=False,
+                 timeline_gap=3, timeline_min_count=3):
         super().__init__(k8s_client, engine)
         self.window = window
         self.z_threshold = z_threshold
         self.anomaly_topk = anomaly_topk
+        # timeline=True: the bulk path scores with krca_rolling_timeline (same pass, same scores) and
+        # the result gains the additive key "anomaly_timeline": when each reported anomaly began
+        self.timeline = bool(timeline)
+        self.timeline_gap = timeline_gap
+        self.timeline_min_count = timeline_min_count
         self.last_scores = None  # device outputs of the last bulk run (used by the Coordinator)
 
     # ------------------------------------------------------------------------------------
@@ -52,10 +58,12 @@ class MetricsAgent(BaseAgent):
         try:
             self._maybe_set_context(context)
             bulk = getattr(self.k8s_client, "get_pod_metric_tensor", None)
-            anomalies = None
+            anomalies = timeline = None
             if bulk is not None:
                 names, x = bulk(namespace)
                 pods, flags, anomalies = self._score_tensor(names, x)
+                if self.timeline and self.last_scores is not None:
+                    timeline = self._anomaly_timeline(names, anomalies, self.last_scores)
             else:
                 pod_metrics = self.k8s_client.get_pod_metrics(namespace)
                 pods, flags = self._score_dict(pod_metrics)
@@ -68,6 +76,8 @@ class MetricsAgent(BaseAgent):
             res = self.get_results()
             if anomalies is not None:
                 res["anomalies"] = anomalies
+            if timeline is not None:
+                res["anomaly_timeline"] = timeline
             return res
         except Exception as e:  # ref:agents/metrics_agent.py:58-67
             return self._error_result("metrics", e)
@@ -95,7 +105,11 @@ class MetricsAgent(BaseAgent):
         T, P, M = x.shape
         if P == 0:
             return [], None, []
-        out = self.engine.rolling_score(x, window=self.window, z_threshold=self.z_threshold)
+        if self.timeline:
+            out = self.engine.rolling_timeline(x, window=self.window, z_threshold=self.z_threshold,
+                                               gap=self.timeline_gap, min_count=self.timeline_min_count)
+        else:
+            out = self.engine.rolling_score(x, window=self.window, z_threshold=self.z_threshold)
         self.last_scores = out
         flags = out["flags"]
         flagged = np.nonzero(flags & (F_CPU80 | F_MEM80))[0]
@@ -116,6 +130,19 @@ class MetricsAgent(BaseAgent):
                 "deviation": float(s),
             })
         return pods, flags, anomalies
+
+    def _anomaly_timeline(self, names, anomalies, out):
+        """Per reported anomaly, in the order of `anomalies`: onset step, last step, episode count,
+        lead metric and number of metrics involved (onset_step -1: the pod is anomalous at the last
+        step but has no sustained episode)."""
+        index = {f"Pod/{n}": p for p, n in enumerate(names)} if anomalies else {}
+        rows = []
+        for a in anomalies:
+            p = index[a["resource"]]
+            rows.append({"resource": a["resource"], "onset_step": int(out["onset_host"][p]),
+                         "last_step": int(out["last_host"][p]), "episode_count": int(out["count_host"][p]),
+                         "lead_metric": int(out["lead_host"][p]), "n_metrics": int(out["n_metrics_host"][p])})
+        return rows
 
     # -- shared reporting (ref:agents/metrics_agent.py:69-161) ---------------------------
     def _report_usage(self, pods, flags, label, key, ch, f80, f90):

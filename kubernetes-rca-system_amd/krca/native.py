@@ -28,6 +28,11 @@ SIGNATURES = {
     "krca_rolling_score_variant": (c_i32, [c_i64, c_i32, c_i32, c_i32]),
     "krca_usage_flags": (c_i32, [c_vp, c_i64, c_vp, c_vp]),
     "krca_rolling_score": (c_i32, [c_vp, c_i64, c_i32, c_i32, c_i32, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "krca_rolling_timeline": (c_i32, [c_vp, c_i64, c_i32, c_i32, c_i32, c_f32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp,
+                                      c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "krca_rca_precede_ws_size": (c_i64, [c_i64]),
+    "krca_rca_precede": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "krca_rca_first_mover_key": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp]),
     "krca_stream_state_size": (c_i64, [c_i64, c_i32, c_i32, c_i32]),
     "krca_stream_score": (c_i32, [c_vp, c_i64, c_i32, c_i32, c_i64, c_i32, c_i32, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp,
                                   c_vp]),
@@ -313,6 +318,123 @@ class NativeEngine:
         res = dict(d)
         res["flags"] = d["flags"].cpu().numpy()
         res["n_exceed_host"] = d["n_exceed"].cpu().numpy()
+        return res
+
+    # -- a5t: anomaly timeline (include/krca.h, csrc/score.hip, csrc/precede.hip) -------------------
+    TIMELINE_KEYS = ("onset", "last", "count", "peak", "lead", "n_metrics")
+
+    def rolling_timeline_device(self, x, window=60, z_threshold=3.0, gap=3, min_count=3, out=None):
+        """Launch only (no sync): x float32 [T, P, M] on the device -> dict of device tensors: the
+        four outputs of rolling_score_device (bit-identical) plus, per pod, onset / last / count
+        int32, peak float32, lead int8, n_metrics uint8 (krca_rolling_timeline)."""
+        torch = self.torch
+        T, P, M = x.shape
+        new = lambda dt, *shape: torch.empty(shape or (P,), dtype=dt, device=self.device)  # noqa: E731
+        if out is None:
+            out = dict(z_last=new(torch.float32, P, M), score=new(torch.float32), n_exceed=new(torch.int32),
+                       flags=new(torch.uint8), onset=new(torch.int32), last=new(torch.int32), count=new(torch.int32),
+                       peak=new(torch.float32), lead=new(torch.int8), n_metrics=new(torch.uint8))
+        _check(self.lib.krca_rolling_timeline(self.ptr(x), P, M, T, int(window), float(z_threshold), int(gap),
+                                              int(min_count), self.ptr(out["z_last"]), self.ptr(out["score"]),
+                                              self.ptr(out["n_exceed"]), self.ptr(out["flags"]),
+                                              self.ptr(out["onset"]), self.ptr(out["last"]), self.ptr(out["count"]),
+                                              self.ptr(out["peak"]), self.ptr(out["lead"]),
+                                              self.ptr(out["n_metrics"]), self._stream()), "krca_rolling_timeline")
+        return out
+
+    def rolling_timeline(self, x, window=60, z_threshold=3.0, gap=3, min_count=3):
+        """rolling_score's dict (device tensors, flags and n_exceed_host on the host) plus the
+        timeline: device tensors under TIMELINE_KEYS and host copies under '<key>_host'."""
+        x = self._dev(x, self.torch.float32)
+        d = self.rolling_timeline_device(x, window, z_threshold, gap, min_count)
+        res = dict(d)
+        res["flags"] = d["flags"].cpu().numpy()
+        res["n_exceed_host"] = d["n_exceed"].cpu().numpy()
+        for key in self.TIMELINE_KEYS:
+            res[key + "_host"] = d[key].cpu().numpy()
+        res["gap"], res["min_count"] = int(gap), int(min_count)
+        return res
+
+    def rca_precede_device(self, onset, row_ptr, col, slack=0):
+        """krca_rca_precede over the whole pull-CSR (device tensors; onset int32 [N]) -> dict of
+        device tensors dep_earlier, dep_concurrent, caller_later, caller_concurrent, caller_earlier
+        (int32 [N]) and dep_first (int64 [N])."""
+        torch = self.torch
+        N = int(onset.numel())
+        if int(row_ptr.numel()) != N + 1:
+            raise KrcaError(f"rca_precede: row_ptr has {int(row_ptr.numel())} entries for {N} pods")
+        i32 = lambda: torch.empty(N, dtype=torch.int32, device=self.device)  # noqa: E731
+        out = dict(dep_earlier=i32(), dep_concurrent=i32(), caller_later=i32(), caller_concurrent=i32(),
+                   caller_earlier=i32(), dep_first=torch.empty(N, dtype=torch.int64, device=self.device))
+        ws = self._workspace("rca_precede", self.lib.krca_rca_precede_ws_size(N))
+        _check(self.lib.krca_rca_precede(self.ptr(onset), N, int(slack), self.ptr(row_ptr), self.ptr(col),
+                                         self.ptr(out["dep_earlier"]), self.ptr(out["dep_concurrent"]),
+                                         self.ptr(out["dep_first"]), self.ptr(out["caller_later"]),
+                                         self.ptr(out["caller_concurrent"]), self.ptr(out["caller_earlier"]),
+                                         self.ptr(ws), self._stream()), "krca_rca_precede")
+        return out
+
+    def _csr_dev(self, row_ptr, col):
+        """Pull-CSR as device tensors; host columns are range-checked (the kernels index by them)."""
+        torch = self.torch
+        if not isinstance(col, torch.Tensor):
+            col = np.ascontiguousarray(col, np.int32)
+            n = len(row_ptr) - 1
+            if len(col) and (int(col.min()) < 0 or int(col.max()) >= n):
+                raise KrcaError(f"pull-CSR column outside [0, {n})")
+            if len(col) == 0:
+                col = np.zeros(1, np.int32)
+        if not isinstance(row_ptr, torch.Tensor):
+            row_ptr = np.ascontiguousarray(row_ptr, np.int64)
+        return self._dev(row_ptr), self._dev(col)
+
+    def rca_precede(self, onset, row_ptr, col, slack=0):
+        """Host or device arrays in, dict of host arrays out (see rca_precede_device)."""
+        torch = self.torch
+        on = self._dev(onset, torch.int32) if isinstance(onset, torch.Tensor) else self._dev(np.asarray(onset, np.int32))
+        rp, cl = self._csr_dev(row_ptr, col)
+        return {key: v.cpu().numpy() for key, v in self.rca_precede_device(on, rp, cl, slack).items()}
+
+    def first_mover_key_device(self, onset, peak, prec):
+        torch = self.torch
+        N = int(onset.numel())
+        key = torch.empty(N, dtype=torch.int64, device=self.device)
+        _check(self.lib.krca_rca_first_mover_key(self.ptr(onset), self.ptr(peak), self.ptr(prec["dep_earlier"]),
+                                                 self.ptr(prec["caller_later"]), self.ptr(prec["caller_concurrent"]),
+                                                 N, self.ptr(key), self._stream()), "krca_rca_first_mover_key")
+        return key
+
+    def first_movers(self, timeline, row_ptr, col, slack=0, k=10, explain=()):
+        """The first movers of a timeline (rolling_timeline / rolling_timeline_device output) over
+        the pull-CSR: pods with an onset and no dependency that went bad more than `slack` steps
+        before them, ranked by the callers that follow them (later or concurrent onsets), then by peak.
+        -> dict of host arrays over the selected pods (at most k <= 16, krca_topk_i64's limit; pods
+        that are no first movers are never selected): idx, onset, lead, peak, followers; `explained` maps each pod of `explain`
+        that has an earlier dependency to (that dependency -- the earliest, then the lowest id -- and
+        its lead over the pod in steps)."""
+        torch = self.torch
+        onset, peak = timeline["onset"], timeline["peak"]
+        N = int(onset.numel())
+        rp, cl = self._csr_dev(row_ptr, col)
+        prec = self.rca_precede_device(onset, rp, cl, slack)
+        key = self.first_mover_key_device(onset, peak, prec)
+        idx, val = self.topk_device(key, min(int(k), N))
+        idx, val = idx.cpu().numpy(), val.cpu().numpy()
+        idx = idx[val > 0].astype(np.int64)
+        sel = torch.from_numpy(idx).to(self.device)
+        take = lambda t: t.index_select(0, sel).cpu().numpy()  # noqa: E731
+        res = dict(idx=idx.astype(np.int32), onset=take(onset), lead=take(timeline["lead"]), peak=take(peak),
+                   followers=take(prec["caller_later"]) + take(prec["caller_concurrent"]), explained={})
+        pods = np.asarray(list(explain), np.int64)
+        if len(pods):
+            from .timeline import decode_dep_first
+            ps = torch.from_numpy(pods).to(self.device)
+            first = prec["dep_first"].index_select(0, ps).cpu().numpy()
+            own = onset.index_select(0, ps).cpu().numpy()
+            for p, f, o in zip(pods.tolist(), first.tolist(), own.tolist()):
+                dep = decode_dep_first(f)
+                if dep is not None:
+                    res["explained"][p] = (dep[1], int(o) - dep[0])
         return res
 
     def gather_last(self, x, idx):

@@ -11,7 +11,8 @@ b ~ U(25,55), a ~ U(0,12), sigma ~ U(0.5,3) (SURVEY.md §8d proposes U(10,60)/U(
 ranges keep the noise off the 0/100 clamps, where flat windows give meaningless z-scores); R root pods get a +12 sigma spike on the last
 `spike_steps` samples and their callers (hop h = 1..3) a +5*0.8^(h-1) sigma spike, so the
 current-step z-scores the scorer reports (|z| at t = T-1 against the trailing window) single
-them out.  Channel 0 = CPU %, 1 = memory %.
+them out.  Channel 0 = CPU %, 1 = memory %.  make_metrics_onsets plants the same faults as level
+shifts with a beginning (root first, hop h `delay` steps later each) for the anomaly timeline.
 Graph model: pods grouped into services of 20; services wired by preferential attachment
 (caller -> callee); each pod calls ~deg pods of its service's callees; no self loops, no
 duplicate edges; edge direction symptom(caller) -> dependency.
@@ -204,6 +205,42 @@ def make_metrics(n_pods, n_metrics=8, n_steps=1440, window=60, seed=0, roots=(),
             pr = torch.as_tensor(np.asarray(pods), device=device)
             x[w0:, pr, :] = (x[w0:, pr, :] + (hop_sigma * hop_decay ** h) * sig[pr]).clamp_(0.0, 100.0)
     return x
+
+
+def make_metrics_onsets(n_pods, n_metrics=8, n_steps=1440, window=60, seed=0, roots=(), hop_sets=(), device="cpu",
+                        t_root=None, delay=5, jitter=2, root_sigma=12.0, hop_sigma=5.0, hop_decay=0.8, **kw):
+    """make_metrics' background (same seed -> the same samples) with faults that have a beginning:
+    each root's metrics shift up by root_sigma * sigma from its onset step to the end of the series,
+    the pods of hop_sets[h] by hop_sigma * hop_decay^h * sigma.  Onset = t_root + hop * delay + U{-jitter
+    .. jitter} (roots are hop 0, hop_sets[h] hop h + 1; seeded; clipped to [window, T - 1]); t_root
+    defaults to T - 200.  A pod listed more than once keeps its first (lowest-hop) onset.
+    -> (x float32 [T, P, M] on `device`, onsets int32 [P] host array, -1 = nothing planted)."""
+    import torch
+    P, M, T = n_pods, n_metrics, n_steps
+    x = make_metrics(P, M, T, window=window, seed=seed, device=device, **kw)
+    g = torch.Generator(device=device)  # make_metrics' first draws: b, a, then the per-series sigma
+    g.manual_seed(int(seed))
+    torch.rand((P, M), generator=g, device=device)
+    torch.rand((P, M), generator=g, device=device)
+    sig = torch.rand((P, M), generator=g, device=device) * 2.5 + 0.5
+    rng = np.random.default_rng(int(seed) + 31337)
+    t_root = T - 200 if t_root is None else int(t_root)
+    onsets = np.full(P, -1, np.int32)
+    amp = np.zeros(P, np.float32)
+    groups = [(np.asarray(roots, np.int64), 0, root_sigma)]
+    groups += [(np.asarray(h, np.int64), i + 1, hop_sigma * hop_decay ** i) for i, h in enumerate(hop_sets)]
+    for pods, hop, mult in groups:
+        jit = rng.integers(-int(jitter), int(jitter) + 1, len(pods))
+        on = np.clip(t_root + hop * int(delay) + jit, min(window, T - 1), T - 1).astype(np.int32)
+        new = onsets[pods] < 0
+        onsets[pods[new]] = on[new]
+        amp[pods[new]] = mult
+    for t in np.unique(onsets[onsets >= 0]).tolist():
+        sel = np.flatnonzero(onsets == t)
+        pr = torch.as_tensor(sel, device=device)
+        shift = torch.as_tensor(amp[sel], device=device).view(-1, 1) * sig[pr]
+        x[t:, pr, :] = (x[t:, pr, :] + shift).clamp_(0.0, 100.0)
+    return x, onsets
 
 
 def make_metrics_range(lo, hi, n_metrics=8, n_steps=1440, window=60, seed=0, roots=(), hop_sets=(), device="cpu",
