@@ -44,12 +44,12 @@ int krca_version(void);
 const char* krca_last_error(void);
 int krca_device_count(int* n_host);
 
-/* Kernel-development A/B switches: KRCA_SCORE_IMPL, KRCA_SCORE_CHUNK, KRCA_SCORE_NT, KRCA_PPR_GRID, KRCA_PPR_DICT,
- * KRCA_LOG_IMPL, KRCA_GROUP_IMPL, KRCA_CORR_DEBUG, KRCA_CORR_RS_GRID, KRCA_CORR_BATCH, KRCA_CORR_AMB_TILE,
- * KRCA_PPR_FUSE, KRCA_PPR_NT, KRCA_PPR_XCD, KRCA_LOG_FUSED, KRCA_CORR_RS_GROUP, KRCA_CORR_SIDE, KRCA_CORR_RS_Q16,
- * KRCA_CORR_CAPC, KRCA_CORR_KM_EXTRA, KRCA_CORR_RSG_GRID, KRCA_CORR_PROJ, KRCA_CORR_PERSIST, KRCA_TRACE_IMPL.  Initialised once from the environment variables
- * of the same names when the library loads; launchers never call getenv.  Process-global, not
- * thread-safe (set them before launching work).  Unknown names: KRCA_EINVAL. */
+/* Kernel-development switches and test hooks: KRCA_SCORE_IMPL, KRCA_PPR_GRID, KRCA_PPR_DICT, KRCA_LOG_IMPL, KRCA_CORR_DEBUG,
+ * KRCA_CORR_RS_GRID, KRCA_CORR_BATCH, KRCA_CORR_AMB_TILE, KRCA_PPR_FUSE, KRCA_PPR_NT, KRCA_PPR_XCD, KRCA_LOG_FUSED,
+ * KRCA_CORR_RS_GROUP, KRCA_CORR_SIDE, KRCA_CORR_RS_Q16, KRCA_CORR_CAPC, KRCA_CORR_KM_EXTRA, KRCA_CORR_RSG_GRID,
+ * KRCA_CORR_PROJ, KRCA_TRACE_IMPL (meanings and defaults: csrc/krca_common.h).  Initialised once from the
+ * environment variables of the same names when the library loads; launchers never call getenv.  Process-global,
+ * not thread-safe (set them before launching work).  Unknown names: KRCA_EINVAL. */
 int krca_tune_set(const char* name, int32_t value);
 int krca_tune_get(const char* name, int32_t* value_host);
 
@@ -74,13 +74,14 @@ int krca_rolling_score(const float* x, int64_t P, int32_t M, int32_t T, int32_t 
 /* which kernel krca_rolling_score launches for these sizes (host query, no device work):
  * KRCA_SCORE_PIPE software-pipelined chunks (the default), KRCA_SCORE_PIPE_ROWS the same with one
  * buffer descriptor per row (series counts past the 2^31-byte descriptor range),
- * KRCA_SCORE_RING plain loads, KRCA_SCORE_RING_BUF W-block buffer loads, KRCA_SCORE_REREAD any W. */
+ * KRCA_SCORE_RING plain loads (T <= W), KRCA_SCORE_REREAD any W.  The knob KRCA_SCORE_IMPL = 1 / 4
+ * forces KRCA_SCORE_RING / KRCA_SCORE_PIPE_ROWS at T > W (how tests reach them at small shapes);
+ * any other non-zero value behaves as 0.  The codes 2 and 5 belonged to removed kernels: retired,
+ * not reused. */
 #define KRCA_SCORE_PIPE 0
 #define KRCA_SCORE_RING 1
-#define KRCA_SCORE_RING_BUF 2
 #define KRCA_SCORE_REREAD 3
 #define KRCA_SCORE_PIPE_ROWS 4
-#define KRCA_SCORE_LDS 5 /* A/B (KRCA_SCORE_IMPL=5, W = 60): rows staged by LDS-DMA, 1 KiB per wave instruction */
 int krca_rolling_score_variant(int64_t P, int32_t M, int32_t T, int32_t W);
 
 /* ---- a5t: anomaly timeline -- WHEN each pod went bad (new primitive; plugs in at
@@ -140,7 +141,9 @@ int krca_rca_first_mover_key(const int32_t* onset, const float* peak, const int3
  * device so they cannot fault, but the results are then unspecified).
  * Lines are str.splitlines() lines; a line is in category c iff
  * re.search(pattern_c, line, re.IGNORECASE) (compiled DFA, csrc/log_dfa_tables.h).
- * Two phases (the line count is data-dependent):
+ * krca_log_scan below is the one-call protocol.  The two-call protocol (the line count is
+ * data-dependent), which a caller may use on its own and which finishes a krca_log_scan whose line
+ * arrays were too small:
  *   krca_log_index: per-chunk line-start counts + scan into block_base (workspace of
  *                   krca_log_index_size(nbytes) int64) and *n_lines (device int64).
  *   krca_log_match: (same workspace; it also keeps the first line id of every 256-byte chunk

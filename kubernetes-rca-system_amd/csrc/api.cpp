@@ -18,44 +18,41 @@ int env_int(const char* name, int dflt) {
   const char* e = getenv(name);
   return e ? atoi(e) : dflt;
 }
+// every knob once: its name (environment variable and krca_tune_set / krca_tune_get key), its field
+// and its default (the one krca_common.h documents)
 struct NamedKnob {
   const char* name;
   int Tuning::*field;
+  int dflt;
 };
 const NamedKnob kKnobs[] = {
-    {"KRCA_SCORE_IMPL", &Tuning::score_impl}, {"KRCA_SCORE_CHUNK", &Tuning::score_chunk},
-    {"KRCA_SCORE_NT", &Tuning::score_nt},     {"KRCA_PPR_GRID", &Tuning::ppr_grid},
-    {"KRCA_PPR_DICT", &Tuning::ppr_dict},
-    {"KRCA_LOG_IMPL", &Tuning::log_impl},     {"KRCA_GROUP_IMPL", &Tuning::group_impl},
-    {"KRCA_CORR_DEBUG", &Tuning::corr_debug},
-    {"KRCA_CORR_RS_GRID", &Tuning::corr_rs_grid},
-    {"KRCA_CORR_BATCH", &Tuning::corr_batch},
-    {"KRCA_CORR_AMB_TILE", &Tuning::corr_amb_tile},
-    {"KRCA_PPR_FUSE", &Tuning::ppr_fuse},
-    {"KRCA_PPR_NT", &Tuning::ppr_nt},
-    {"KRCA_PPR_XCD", &Tuning::ppr_xcd},
-    {"KRCA_LOG_FUSED", &Tuning::log_fused},
-    {"KRCA_CORR_RS_GROUP", &Tuning::corr_rs_group},
-    {"KRCA_CORR_SIDE", &Tuning::corr_side},
-    {"KRCA_CORR_RS_Q16", &Tuning::corr_rs_q16},
-    {"KRCA_CORR_CAPC", &Tuning::corr_capc},
-    {"KRCA_CORR_KM_EXTRA", &Tuning::corr_km_extra},
-    {"KRCA_CORR_RSG_GRID", &Tuning::corr_rsg_grid},
-    {"KRCA_CORR_PROJ", &Tuning::corr_proj},
-    {"KRCA_CORR_PERSIST", &Tuning::corr_persist},
-    {"KRCA_TRACE_IMPL", &Tuning::trace_impl},
+    {"KRCA_SCORE_IMPL", &Tuning::score_impl, 0},
+    {"KRCA_PPR_GRID", &Tuning::ppr_grid, 0},
+    {"KRCA_PPR_DICT", &Tuning::ppr_dict, 1},
+    {"KRCA_LOG_IMPL", &Tuning::log_impl, 0},
+    {"KRCA_CORR_DEBUG", &Tuning::corr_debug, 0},
+    {"KRCA_CORR_RS_GRID", &Tuning::corr_rs_grid, 1024},
+    {"KRCA_CORR_BATCH", &Tuning::corr_batch, 0},
+    {"KRCA_CORR_AMB_TILE", &Tuning::corr_amb_tile, -1},
+    {"KRCA_PPR_FUSE", &Tuning::ppr_fuse, 0},
+    {"KRCA_PPR_NT", &Tuning::ppr_nt, 0},
+    {"KRCA_PPR_XCD", &Tuning::ppr_xcd, 0},
+    {"KRCA_LOG_FUSED", &Tuning::log_fused, 0},
+    {"KRCA_CORR_RS_GROUP", &Tuning::corr_rs_group, 1},
+    {"KRCA_CORR_SIDE", &Tuning::corr_side, 0},
+    {"KRCA_CORR_RS_Q16", &Tuning::corr_rs_q16, 1},
+    {"KRCA_CORR_CAPC", &Tuning::corr_capc, 0},
+    {"KRCA_CORR_KM_EXTRA", &Tuning::corr_km_extra, 6},
+    {"KRCA_CORR_RSG_GRID", &Tuning::corr_rsg_grid, 0},
+    {"KRCA_CORR_PROJ", &Tuning::corr_proj, 2},
+    {"KRCA_TRACE_IMPL", &Tuning::trace_impl, 0},
 };
-Tuning g_tune = {env_int("KRCA_SCORE_IMPL", 0), env_int("KRCA_SCORE_CHUNK", 20), env_int("KRCA_SCORE_NT", 1),
-                 env_int("KRCA_PPR_GRID", 0),   env_int("KRCA_PPR_DICT", 1),     env_int("KRCA_LOG_IMPL", 0),
-                 env_int("KRCA_GROUP_IMPL", 0),
-                 env_int("KRCA_CORR_DEBUG", 0), env_int("KRCA_CORR_RS_GRID", 1024),
-                 env_int("KRCA_CORR_BATCH", 0),   env_int("KRCA_CORR_AMB_TILE", -1),
-                 env_int("KRCA_PPR_FUSE", 0), env_int("KRCA_PPR_NT", 0),
-                 env_int("KRCA_PPR_XCD", 0), env_int("KRCA_LOG_FUSED", 0), env_int("KRCA_CORR_RS_GROUP", 1),
-                 env_int("KRCA_CORR_SIDE", 0), env_int("KRCA_CORR_RS_Q16", 1),
-                 env_int("KRCA_CORR_CAPC", 0), env_int("KRCA_CORR_KM_EXTRA", 6),
-                 env_int("KRCA_CORR_RSG_GRID", 0), env_int("KRCA_CORR_PROJ", 2),
-                 env_int("KRCA_CORR_PERSIST", 0), env_int("KRCA_TRACE_IMPL", 0)};
+Tuning tuning_from_env() {
+  Tuning t{};
+  for (const NamedKnob& k : kKnobs) t.*(k.field) = env_int(k.name, k.dflt);
+  return t;
+}
+Tuning g_tune = tuning_from_env();
 const NamedKnob* find_knob(const char* name) {
   if (!name) return nullptr;
   for (const NamedKnob& k : kKnobs)

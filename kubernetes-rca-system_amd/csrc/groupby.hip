@@ -50,7 +50,7 @@ __global__ __launch_bounds__(TPB) void group_init(int32_t S, int64_t* __restrict
 }
 
 // PASS 0: first / count / n_key / top[0].  PASS r>0: top[r] below top[r-1].
-template <bool PASS0, bool PEEL>
+template <bool PASS0>
 __global__ __launch_bounds__(TPB) void group_pass(const int32_t* __restrict__ slot, const int64_t* __restrict__ key,
                                                   int64_t N, int32_t S, int r, int64_t* __restrict__ rec) {
   const int lane = threadIdx.x & 63;
@@ -67,17 +67,6 @@ __global__ __launch_bounds__(TPB) void group_pass(const int32_t* __restrict__ sl
         const int64_t lim = rec[(int64_t)s * REC + 1 + r];  // top[r-1]
         if (!(k >= 0 && k < lim)) s = -1;  // only keys strictly below the previous rank compete
       }
-    }
-    if (!PEEL) {  // A/B variant (KRCA_GROUP_IMPL=1): every lane issues its own atomics
-      if (s >= 0) {
-        int64_t* rp = rec + (int64_t)s * REC;
-        if (PASS0) {
-          atomicMin((long long*)rp, (long long)i);
-          atomicAdd((unsigned long long*)(rp + 1), (1ull << 32) | (k >= 0 ? 1u : 0u));
-        }
-        if (k >= 0) atomicMax((long long*)(rp + 2 + r), (long long)k);
-      }
-      continue;
     }
     uint64_t act = __ballot(s >= 0);
     while (act) {  // wave-uniform: act is a ballot
@@ -124,19 +113,10 @@ int krca_group_reduce(const int32_t* slot, const int64_t* key, int64_t N, int64_
   KRCA_LAUNCH_CHECK();
   if (N == 0) return KRCA_OK;
   KRCA_CHECK_ARG(slot && key, "krca_group_reduce: null input");
-  const int impl = krca::tuning().group_impl;
-  if (impl == 1)
-    hipLaunchKernelGGL((group_pass<true, false>), dim3(grid_for(N)), dim3(TPB), 0, st, slot, key, N, S, 0, rec);
-  else
-    hipLaunchKernelGGL((group_pass<true, true>), dim3(grid_for(N)), dim3(TPB), 0, st, slot, key, N, S, 0, rec);
+  hipLaunchKernelGGL(group_pass<true>, dim3(grid_for(N)), dim3(TPB), 0, st, slot, key, N, S, 0, rec);
   KRCA_LAUNCH_CHECK();
   for (int r = 1; r < R && n_ranked > 0; ++r) {
-    if (impl == 1)
-      hipLaunchKernelGGL((group_pass<false, false>), dim3(grid_for(n_ranked)), dim3(TPB), 0, st, slot, key, n_ranked,
-                         S, r, rec);
-    else
-      hipLaunchKernelGGL((group_pass<false, true>), dim3(grid_for(n_ranked)), dim3(TPB), 0, st, slot, key, n_ranked,
-                         S, r, rec);
+    hipLaunchKernelGGL(group_pass<false>, dim3(grid_for(n_ranked)), dim3(TPB), 0, st, slot, key, n_ranked, S, r, rec);
     KRCA_LAUNCH_CHECK();
   }
   return KRCA_OK;

@@ -1984,26 +1984,52 @@ int64_t num_tiles(int64_t nbytes) { return std::max<int64_t>(1, krca::ceil_div(n
 // int64 words of the int32 long-line queue (lines longer than LONG_LINE: at most nbytes / LONG_LINE,
 // + one per tile whose last line runs past its LOOK bytes)
 int64_t long_q_words(int64_t nbytes) { return krca::ceil_div(nbytes / LONG_LINE + 2 * num_tiles(nbytes) + 2, 2); }
-// krca_log_scan's tail of the workspace (int64 words): look-back status words for the 2 x num_tiles
-// 32 KiB tiles of log_index_match (num_tiles of log_index_lines use the first half), the tile ticket
-int64_t scan_tail_words(int64_t nbytes) { return 2 * num_tiles(nbytes) + 1; }
+// views into a caller's workspace of krca_log_index_size(nbytes) int64 words; every entry point
+// takes them from log_ws (ws == nullptr: only `words`, the size, is meaningful)
+struct LogWs {
+  int64_t nt;                  // 64 KiB tiles
+  int64_t* tile;               // [nt + 1] first line id of each tile; tile[nt] = the line count
+  int32_t* chunk;              // [nt * TPB] line starts per 256-byte chunk
+  int32_t* cdoc;               // [nt * TPB] chunk -> container of its first byte
+  int64_t* chunk_line0;        // [nt * TPB] first line id per chunk
+  int32_t* n_long;             // [1] long-line count
+  int32_t* long_q;             // [2 * long_q_words] long-line queue
+  unsigned long long* status;  // [2 * nt] look-back status words (krca_log_scan): one per 32 KiB tile of
+                               // log_index_match (the nt tiles of log_index_lines use the first half)
+  unsigned int* ticket;        // [1] tile ticket (krca_log_scan)
+  int64_t words;
+};
+
+LogWs log_ws(int64_t* ws, int64_t nbytes) {
+  LogWs w{};
+  w.nt = num_tiles(nbytes);
+  int64_t o = 0;
+  auto take = [&](int64_t words) {
+    int64_t* p = ws ? ws + o : nullptr;
+    o += words;
+    return p;
+  };
+  const int64_t chunks = w.nt * TPB;
+  w.tile = take(w.nt + 1);
+  w.chunk = reinterpret_cast<int32_t*>(take(krca::ceil_div(chunks, 2)));
+  w.cdoc = reinterpret_cast<int32_t*>(take(krca::ceil_div(chunks, 2) + 2));  // (two spare words)
+  w.chunk_line0 = take(chunks);
+  w.n_long = reinterpret_cast<int32_t*>(take(1));
+  w.long_q = reinterpret_cast<int32_t*>(take(long_q_words(nbytes)));
+  w.status = reinterpret_cast<unsigned long long*>(take(2 * w.nt));
+  w.ticket = reinterpret_cast<unsigned int*>(take(1));
+  w.words = o;
+  return w;
+}
 
 }  // namespace
 
 extern "C" {
 
-// workspace (int64 units): [ntiles+1] tile base | [ntiles*TPB] int32 chunk counts |
-// [ntiles*TPB] int32 chunk -> container | [ntiles*TPB] int64 first line id per chunk |
-// [1] long-line count | int32 long-line queue [long_q_words] | [ntiles] look-back status |
-// [1] tile ticket (the last two: krca_log_scan)
 const char* krca_log_dfa_unicode(void) { return KRCA_DFA_UNIDATA; }
 uint64_t krca_log_dfa_digest(void) { return KRCA_DFA_DIGEST; }
 
-int64_t krca_log_index_size(int64_t nbytes) {
-  const int64_t nt = num_tiles(nbytes);
-  return (nt + 1) + 2 * krca::ceil_div(nt * TPB, 2) + 2 + nt * TPB + 1 + long_q_words(nbytes) +
-         scan_tail_words(nbytes);  // + krca_log_scan's look-back status words, ticket, deferred-line queue
-}
+int64_t krca_log_index_size(int64_t nbytes) { return log_ws(nullptr, nbytes).words; }
 
 int krca_log_index(const uint8_t* text, int64_t nbytes, const int64_t* doc_off, int64_t ndocs, int64_t* ws,
                    int64_t* n_lines, void* stream) {
@@ -2011,20 +2037,18 @@ int krca_log_index(const uint8_t* text, int64_t nbytes, const int64_t* doc_off, 
   KRCA_CHECK_ARG(doc_off && ws && n_lines, "krca_log_index: null pointer");
   KRCA_CHECK_ARG(nbytes == 0 || text, "krca_log_index: null text");
   KRCA_CHECK_ARG(((uintptr_t)text & 15) == 0, "krca_log_index: text must be 16-byte aligned");
-  const int64_t nt = num_tiles(nbytes);
   KRCA_CHECK_ARG(ndocs < INT32_MAX, "krca_log_index: too many containers");
-  int64_t* tile = ws;
-  int32_t* chunk = reinterpret_cast<int32_t*>(ws + nt + 1);
-  int32_t* cdoc = chunk + 2 * krca::ceil_div(nt * TPB, 2);
+  const LogWs w = log_ws(ws, nbytes);
+  const int64_t nt = w.nt;
   hipStream_t st = krca::as_stream(stream);
-  KRCA_HIP(hipMemsetAsync(cdoc, 0, nt * TPB * sizeof(int32_t), st));  // defined map even off-contract
+  KRCA_HIP(hipMemsetAsync(w.cdoc, 0, nt * TPB * sizeof(int32_t), st));  // defined map even off-contract
   hipLaunchKernelGGL(log_chunk_doc, dim3((unsigned)krca::ceil_div(ndocs, TPB)), dim3(TPB), 0, st, doc_off, ndocs,
-                     nbytes, cdoc, (unsigned long long*)nullptr, (int64_t)0, (int32_t*)nullptr);
+                     nbytes, w.cdoc, (unsigned long long*)nullptr, (int64_t)0, (int32_t*)nullptr);
   KRCA_LAUNCH_CHECK();
   hipLaunchKernelGGL(log_count, dim3((unsigned)nt), dim3(TPB), 0, st, text, nbytes, doc_off, ndocs,
-                     (const int32_t*)cdoc, chunk, tile);
+                     (const int32_t*)w.cdoc, w.chunk, w.tile);
   KRCA_LAUNCH_CHECK();
-  hipLaunchKernelGGL(log_scan, dim3(1), dim3(1024), 0, st, tile, nt, n_lines);
+  hipLaunchKernelGGL(log_scan, dim3(1), dim3(1024), 0, st, w.tile, nt, n_lines);
   KRCA_LAUNCH_CHECK();
   return KRCA_OK;
 }
@@ -2036,13 +2060,12 @@ int krca_log_match(const uint8_t* text, int64_t nbytes, const int64_t* doc_off, 
   KRCA_CHECK_ARG(doc_off && ws && doc_lines && hist, "krca_log_match: null pointer");
   KRCA_CHECK_ARG(((uintptr_t)text & 15) == 0, "krca_log_match: text must be 16-byte aligned");
   KRCA_CHECK_ARG(n_lines == 0 || (line_start && line_end && line_mask), "krca_log_match: null line arrays");
-  const int64_t nt = num_tiles(nbytes);
-  const int64_t* tile = ws;
-  const int32_t* chunk = reinterpret_cast<const int32_t*>(ws + nt + 1);
-  const int32_t* cdoc = chunk + 2 * krca::ceil_div(nt * TPB, 2);
-  int64_t* chunk_line0 = ws + (nt + 1) + 2 * krca::ceil_div(nt * TPB, 2) + 2;
-  int32_t* n_long = reinterpret_cast<int32_t*>(chunk_line0 + nt * TPB);
-  int32_t* long_q = reinterpret_cast<int32_t*>(chunk_line0 + nt * TPB + 1);
+  const LogWs w = log_ws(ws, nbytes);
+  const int64_t nt = w.nt;
+  const int64_t* tile = w.tile;
+  const int32_t *chunk = w.chunk, *cdoc = w.cdoc;
+  int64_t* chunk_line0 = w.chunk_line0;
+  int32_t *n_long = w.n_long, *long_q = w.long_q;
   hipStream_t st = krca::as_stream(stream);
   const int impl = krca::tuning().log_impl;  // A/B: tests switch it with krca_tune_set
   if (n_lines > 0 && impl == 1) {  // A/B: lane per 256-byte chunk, DFA and line logic in one pass
@@ -2090,23 +2113,16 @@ int krca_log_scan(const uint8_t* text, int64_t nbytes, const int64_t* doc_off, i
   KRCA_CHECK_ARG(nbytes == 0 || text, "krca_log_scan: null text");
   KRCA_CHECK_ARG(((uintptr_t)text & 15) == 0, "krca_log_scan: text must be 16-byte aligned");
   KRCA_CHECK_ARG(line_cap == 0 || (line_start && line_end && line_mask), "krca_log_scan: null line arrays");
-  const int64_t nt = num_tiles(nbytes);
-  int64_t* tile = ws;  // tile[nt] = the line count, on the device
-  int32_t* chunk = reinterpret_cast<int32_t*>(ws + nt + 1);
-  int32_t* cdoc = chunk + 2 * krca::ceil_div(nt * TPB, 2);
-  int64_t* chunk_line0 = ws + (nt + 1) + 2 * krca::ceil_div(nt * TPB, 2) + 2;
-  int32_t* n_long = reinterpret_cast<int32_t*>(chunk_line0 + nt * TPB);
-  int32_t* long_q = reinterpret_cast<int32_t*>(chunk_line0 + nt * TPB + 1);
-  unsigned long long* status =
-      reinterpret_cast<unsigned long long*>(chunk_line0 + nt * TPB + 1 + long_q_words(nbytes));
-  unsigned int* ticket = reinterpret_cast<unsigned int*>(status + 2 * nt);
+  const LogWs w = log_ws(ws, nbytes);
+  const int64_t nt = w.nt;
+  int64_t* const tile = w.tile;  // tile[nt] = the line count, on the device
   hipStream_t st = krca::as_stream(stream);
   if (nbytes == 0) {
     // no text (the pointer may be null): every container is empty and no kernel may read text --
     // the index pass's unconditional piece loads clamp to the last 16-byte block that holds a
     // byte, and there is none (an empty window faulted there: test_log_scan_degenerate_texts)
     KRCA_HIP(hipMemsetAsync(tile, 0, (nt + 1) * sizeof(int64_t), st));  // tile bases, the line count
-    KRCA_HIP(hipMemsetAsync(chunk_line0, 0, nt * TPB * sizeof(int64_t), st));
+    KRCA_HIP(hipMemsetAsync(w.chunk_line0, 0, nt * TPB * sizeof(int64_t), st));
     KRCA_HIP(hipMemsetAsync(doc_lines, 0, ndocs * sizeof(int32_t), st));
     KRCA_HIP(hipMemsetAsync(hist, 0, ndocs * KRCA_NCAT * sizeof(int32_t), st));
     if (examples) KRCA_HIP(hipMemsetAsync(examples, 0xFF, ndocs * KRCA_NCAT * 3 * sizeof(int32_t), st));  // -1
@@ -2119,7 +2135,7 @@ int krca_log_scan(const uint8_t* text, int64_t nbytes, const int64_t* doc_off, i
   // look-back status words + ticket and long-line count (no memset launches: each dependent
   // launch costs ~10 us at the front of the scan)
   hipLaunchKernelGGL(log_chunk_doc, dim3((unsigned)krca::ceil_div(ndocs, TPB)), dim3(TPB), 0, st, doc_off, ndocs,
-                     nbytes, cdoc, status, 2 * nt + 1, n_long);  // status words, ticket
+                     nbytes, w.cdoc, w.status, 2 * nt + 1, w.n_long);  // status words, ticket
   KRCA_LAUNCH_CHECK();
   const int64_t* Ld = tile + nt;  // the line count, on the device (written by the index's last tile)
   if (krca::tuning().log_fused) {
@@ -2133,8 +2149,8 @@ int krca_log_scan(const uint8_t* text, int64_t nbytes, const int64_t* doc_off, i
       const int64_t resident =
           krca::resident_workgroups(reinterpret_cast<const void*>(&log_index_match<CF>), CF::FTPB, st, 1);
       hipLaunchKernelGGL(log_index_match<CF>, dim3((unsigned)std::min<int64_t>(ntf, resident)), dim3(CF::FTPB), 0, st,
-                         text, nbytes, doc_off, ndocs, (const int32_t*)cdoc, chunk, tile, nt, status, ticket, ntf,
-                         line_cap, line_start, line_end, line_mask, chunk_line0, tile + nt, long_q, n_long);
+                         text, nbytes, doc_off, ndocs, (const int32_t*)w.cdoc, w.chunk, tile, nt, w.status, w.ticket,
+                         ntf, line_cap, line_start, line_end, line_mask, w.chunk_line0, tile + nt, w.long_q, w.n_long);
       return ntf;
     };
     if (krca::tuning().log_fused == 2) launch(FBig{});
@@ -2145,19 +2161,19 @@ int krca_log_scan(const uint8_t* text, int64_t nbytes, const int64_t* doc_off, i
     const int64_t resident = krca::resident_workgroups(reinterpret_cast<const void*>(&log_index_lines), TPB, st, 4);
     const int64_t grid_ix = LOG_IDX_PERSIST ? std::min<int64_t>(nt, resident) : nt;
     hipLaunchKernelGGL(log_index_lines, dim3((unsigned)grid_ix), dim3(TPB), 0, st, text, nbytes, doc_off, ndocs,
-                       (const int32_t*)cdoc, chunk, tile, status, ticket, nt, line_cap, line_start, line_end, chunk_line0,
-                       tile + nt);
+                       (const int32_t*)w.cdoc, w.chunk, tile, w.status, w.ticket, nt, line_cap, line_start, line_end,
+                       w.chunk_line0, tile + nt);
     KRCA_LAUNCH_CHECK();
     const int64_t grid = std::max<int64_t>(1, std::min<int64_t>(krca::ceil_div(line_cap, DFA_TPB), 256 * 3));
     hipLaunchKernelGGL(log_dfa, dim3((unsigned)grid), dim3(DFA_TPB), 0, st, text, nbytes, (int64_t)0, Ld, line_cap,
-                       (const int64_t*)line_start, (const int64_t*)line_end, line_mask, long_q, n_long);
+                       (const int64_t*)line_start, (const int64_t*)line_end, line_mask, w.long_q, w.n_long);
     KRCA_LAUNCH_CHECK();
   }
   hipLaunchKernelGGL(log_dfa_long, dim3(256), dim3(TPB), 0, st, text, nbytes, (const int64_t*)line_start,
-                     (const int64_t*)line_end, line_mask, (const int32_t*)long_q, (const int32_t*)n_long);
+                     (const int64_t*)line_end, line_mask, (const int32_t*)w.long_q, (const int32_t*)w.n_long);
   KRCA_LAUNCH_CHECK();
   hipLaunchKernelGGL(examples ? log_hist<true> : log_hist<false>, dim3((unsigned)krca::ceil_div(ndocs, TPB)), dim3(TPB),
-                     0, st, doc_off, ndocs, (const int64_t*)chunk_line0, nt * TPB, line_start, line_mask, (int64_t)0, Ld,
+                     0, st, doc_off, ndocs, (const int64_t*)w.chunk_line0, nt * TPB, line_start, line_mask, (int64_t)0, Ld,
                      line_cap, doc_lines, hist, examples, doc_line0);
   KRCA_LAUNCH_CHECK();
   KRCA_HIP(hipMemcpyAsync(n_lines_host, Ld, sizeof(int64_t), hipMemcpyDeviceToHost, st));

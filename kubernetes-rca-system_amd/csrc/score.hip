@@ -257,67 +257,16 @@ __global__ __launch_bounds__(256) void rolling_score_ring(const float* __restric
   pod_epilogue(st, epsB, s, active, M, T, xs, S, z_last, score, n_exceed, flags);
 }
 
-// Same arithmetic as rolling_score_ring; addressing for gfx950 buffer loads: per W-step block a
-// wave-uniform buffer descriptor on the block's first row, the lane's 32-bit byte offset in
-// voffset and the row offset j*S*4 in soffset, so a load costs no per-lane address arithmetic
-// (`buffer_load_dword v, v_off, s[rsrc], s_off offen`).  Requires 4*S*W < 2^31.
+// gfx950 buffer loads: a wave-uniform buffer descriptor on a block of rows, the lane's 32-bit byte
+// offset in voffset and the row offset j*S*4 in soffset, so a load costs no per-lane address
+// arithmetic (`buffer_load_dword v, v_off, s[rsrc], s_off offen`).
 template <int AUX = 0>  // cache policy bits: 0 default, 2 = nt (streamed once)
 __device__ __forceinline__ float bload(__amdgpu_buffer_rsrc_t r, uint32_t voff, uint32_t soff) {
   return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, (int)voff, (int)soff, AUX));
 }
 
-template <int W>
-__global__ __launch_bounds__(256) void rolling_score_ring_buf(const float* __restrict__ x, int64_t S, int T, int M,
-                                                              double thr2, float* __restrict__ z_last,
-                                                              float* __restrict__ score,
-                                                              int32_t* __restrict__ n_exceed,
-                                                              uint8_t* __restrict__ flags) {
-  const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const bool active = s < S;
-  const uint32_t voff = active ? (uint32_t)s * 4u : 0u;
-  const uint32_t rowb = (uint32_t)(S * 4);  // bytes per time row
-  const double Wd = (double)W, epsB = kVarEps * Wd * Wd;
-  StepState st{0.0, 0.0, 0, 0.0, 0.0};
-  float ring[W];
-  const int Tw = T < W ? T : W;
-  __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)x, 0, (int)(rowb * (uint32_t)Tw), 0x00020000);
-#pragma unroll
-  for (int j = 0; j < W; ++j) {
-    const float v = j < T ? bload(rs, voff, rowb * j) : 0.f;
-    ring[j] = v;
-    const double vd = (double)v;
-    st.s1 = st.s1 + vd;
-    st.s2 = fma(vd, vd, st.s2);
-  }
-  int t0 = W;
-  for (; t0 + W <= T; t0 += W) {
-    rs = __builtin_amdgcn_make_buffer_rsrc((void*)(x + (int64_t)t0 * S), 0, (int)(rowb * (uint32_t)W), 0x00020000);
-    float nx[W];
-#pragma unroll
-    for (int j = 0; j < W; ++j) nx[j] = bload(rs, voff, rowb * j);
-#pragma unroll
-    for (int j = 0; j < W; ++j) {
-      step(st, nx[j], ring[j], Wd, epsB, thr2, t0 + j == T - 1);
-      ring[j] = nx[j];
-    }
-  }
-  if (t0 < T) {
-    rs = __builtin_amdgcn_make_buffer_rsrc((void*)(x + (int64_t)t0 * S), 0, (int)(rowb * (uint32_t)(T - t0)),
-                                           0x00020000);
-#pragma unroll
-    for (int j = 0; j < W; ++j) {
-      if (t0 + j < T) {
-        const float v = bload(rs, voff, rowb * j);
-        step(st, v, ring[j], Wd, epsB, thr2, t0 + j == T - 1);
-        ring[j] = v;
-      }
-    }
-  }
-  pod_epilogue(st, epsB, s, active, M, T, x + (active ? s : 0), S, z_last, score, n_exceed, flags);
-}
-
-// Software-pipelined form of rolling_score_ring_buf (same arithmetic, same bits).  The time axis
-// is walked in C-row chunks (W % C == 0, so every ring slot index stays static); the loads of
+// Software-pipelined form of rolling_score_ring over buffer loads (same arithmetic, same bits).  The
+// time axis is walked in C-row chunks (W % C == 0, so every ring slot index stays static); the loads of
 // chunk c+1 are issued before chunk c is computed, so each wave keeps C rows (C*256 B) in flight
 // through its whole compute phase instead of alternating load bursts and VALU bursts.  Only the
 // final block (the one holding t = T-1) tracks the last-step A/B, so the steady-state loop has
@@ -442,92 +391,6 @@ __global__ __launch_bounds__(256) void rolling_score_pipe(const float* __restric
   if constexpr (Ep::kTrack) timeline_epilogue(ep, s, active, M, targs.out);
 }
 
-// LDS-DMA form of rolling_score_pipe (KRCA_SCORE_IMPL=5, A/B; same steps in the same order, same
-// bits).  The workgroup's 256 series of a time row are 1 KiB contiguous: ONE wave instruction
-// (global_load_lds_dwordx4, 16 B per lane) lands a whole row in LDS, instead of four 256-B register
-// loads; a C-row chunk is C / 4 such instructions per wave, double-buffered (2 x C KiB), the next
-// chunk's in flight while the current one is stepped from LDS.  Needs S % 4 == 0 (16-B aligned rows);
-// the last workgroup's lanes past S re-read its first piece (their values are never used).
-template <int W, int C, int AUX>
-__global__ __launch_bounds__(256) void rolling_score_lds(const float* __restrict__ x, int64_t S, int T, int M,
-                                                         double thr2, float* __restrict__ z_last,
-                                                         float* __restrict__ score, int32_t* __restrict__ n_exceed,
-                                                         uint8_t* __restrict__ flags) {
-  static_assert(W % C == 0 && C % 4 == 0, "chunk must divide the window and split over 4 waves");
-  constexpr int NC = W / C;
-  __shared__ float stage[2][C][256];
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int64_t s0 = (int64_t)blockIdx.x * 256;
-  const int64_t s = s0 + tid;
-  const bool active = s < S;
-  const int64_t piece = s0 + 4 * lane < S ? s0 + 4 * lane : s0;
-  // rows [t, t + C) of the workgroup's series into stage[buf]; rows >= T are not loaded (never read)
-  auto dma = [&](int buf, int t) {
-#pragma unroll
-    for (int q = 0; q < C / 4; ++q) {
-      const int j = wv + 4 * q;
-      if (t + j < T)
-        __builtin_amdgcn_global_load_lds(x + (int64_t)(t + j) * S + piece,
-                                         (__attribute__((address_space(3))) void*)&stage[buf][j][0], 16, 0, AUX);
-    }
-  };
-  auto landed = [&]() {  // this wave's DMA done, then every wave's
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-  };
-  const double Wd = (double)W, epsB = kVarEps * Wd * Wd;
-  StepState st{0.0, 0.0, 0, 0.0, 0.0};
-  float ring[W];
-  // prologue: chunks 0 .. NC-1 fill the window (requires T > W, checked by the launcher)
-  dma(0, 0);
-#pragma unroll
-  for (int c = 0; c < NC; ++c) {
-    landed();
-    dma((c + 1) & 1, (c + 1) * C);  // the next chunk (chunk NC: the first rows past the window)
-#pragma unroll
-    for (int j = 0; j < C; ++j) ring[c * C + j] = stage[c & 1][j][tid];
-  }
-#pragma unroll
-  for (int j = 0; j < W; ++j) {
-    const double vd = (double)ring[j];
-    st.s1 = st.s1 + vd;
-    st.s2 = fma(vd, vd, st.s2);
-  }
-  int k = NC;  // chunk k = rows [k C, k C + C) is in flight into stage[k & 1]
-  int t0 = W;
-  for (; t0 + W < T; t0 += W) {  // full blocks that do not contain t = T-1
-#pragma unroll
-    for (int c = 0; c < NC; ++c, ++k) {
-      landed();
-      dma((k + 1) & 1, (k + 1) * C);
-      const int b = k & 1;
-#pragma unroll
-      for (int j = 0; j < C; ++j) {
-        const float v = stage[b][j][tid];
-        step(st, v, ring[c * C + j], Wd, epsB, thr2, false);
-        ring[c * C + j] = v;
-      }
-    }
-  }
-  // final block: rows [t0, T), 1..W of them
-#pragma unroll
-  for (int c = 0; c < NC; ++c, ++k) {
-    landed();
-    if (c + 1 < NC) dma((k + 1) & 1, (k + 1) * C);
-    const int b = k & 1;
-#pragma unroll
-    for (int j = 0; j < C; ++j) {
-      const int t = t0 + c * C + j;
-      if (t < T) {
-        const float v = stage[b][j][tid];
-        step(st, v, ring[c * C + j], Wd, epsB, thr2, t == T - 1);
-        ring[c * C + j] = v;
-      }
-    }
-  }
-  pod_epilogue(st, epsB, s, active, M, T, x + (active ? s : 0), S, z_last, score, n_exceed, flags);
-}
-
 // Any W: the outgoing sample x[t-W] is re-read (same values, same arithmetic -> same bits).
 template <class Ep = NoEpisodes>
 __global__ __launch_bounds__(256) void rolling_score_reread(const float* __restrict__ x, int64_t S, int T, int W,
@@ -619,10 +482,84 @@ __global__ __launch_bounds__(256) void stream_score(const float* __restrict__ xn
   pod_epilogue(st, epsB, s, active, M, delta, xn + sl, S, z_last, score, n_exceed, flags);
 }
 
-int rows_per_chunk(int W) {
-  return W == 60 ? krca::tuning().score_chunk : (W == 30 ? 15 : (W == 20 ? 10 : W));
-}
+// rows per pipelined chunk: a divisor of W that keeps 10 .. 20 rows in flight per wave
+constexpr int rows_per_chunk(int W) { return W == 60 ? 20 : (W == 30 ? 15 : (W == 20 ? 10 : W)); }
 bool pipe_window(int W) { return W == 60 || W == 30 || W == 20 || W == 15 || W == 10; }
+
+// the metric stream is read once: non-temporal loads (cache policy nt), 6.17 -> 6.61 TB/s at C4
+// (tools/score_ab.py)
+constexpr int kNt = 2;
+
+struct ScoreCall {
+  const float* x;
+  int64_t S;
+  int T, W, M;
+  double thr2;
+  float* z_last;
+  float* score;
+  int32_t* n_exceed;
+  uint8_t* flags;
+  dim3 grid;
+  hipStream_t st;
+};
+
+template <class Ep>
+void launch_reread(const ScoreCall& c, const typename Ep::Args& ea) {
+  hipLaunchKernelGGL(rolling_score_reread<Ep>, c.grid, dim3(256), 0, c.st, c.x, c.S, c.T, c.W, c.M, c.thr2, c.z_last,
+                     c.score, c.n_exceed, c.flags, ea);
+}
+
+// a window with a compiled-in size.  The ring kernel has no timeline form: the timeline re-reads
+// wherever the scorer runs it (T <= W, or forced).
+template <int W, class Ep>
+void launch_window(int variant, const ScoreCall& c, const typename Ep::Args& ea) {
+  constexpr int C = rows_per_chunk(W);
+  if (variant == KRCA_SCORE_PIPE)
+    hipLaunchKernelGGL((rolling_score_pipe<W, C, kNt, SpanRows, Ep>), c.grid, dim3(256), 0, c.st, c.x, c.S, c.T, c.M,
+                       c.thr2, c.z_last, c.score, c.n_exceed, c.flags, ea);
+  else if (variant == KRCA_SCORE_PIPE_ROWS)
+    hipLaunchKernelGGL((rolling_score_pipe<W, C, kNt, BlockRows, Ep>), c.grid, dim3(256), 0, c.st, c.x, c.S, c.T, c.M,
+                       c.thr2, c.z_last, c.score, c.n_exceed, c.flags, ea);
+  else if constexpr (Ep::kTrack)
+    launch_reread<Ep>(c, ea);
+  else
+    hipLaunchKernelGGL(rolling_score_ring<W>, c.grid, dim3(256), 0, c.st, c.x, c.S, c.T, c.M, c.thr2, c.z_last, c.score,
+                       c.n_exceed, c.flags);
+}
+
+// krca_rolling_score (Ep = NoEpisodes) and krca_rolling_timeline (Episodes): the kernel that
+// krca_rolling_score_variant names for these sizes
+template <class Ep>
+int launch_score(const char* fn, const float* x, int64_t P, int32_t M, int32_t T, int32_t W, float z_thr, float* z_last,
+                 float* score, int32_t* n_exceed, uint8_t* flags, const typename Ep::Args& ea, void* stream) {
+  KRCA_CHECK_ARG(P >= 0 && T >= 0 && W >= 1, "%s: bad sizes P=%lld T=%d W=%d", fn, (long long)P, T, W);
+  KRCA_CHECK_ARG(M >= 1 && M <= 64 && (M & (M - 1)) == 0, "%s: M=%d must be a power of two <= 64", fn, M);
+  bool outs = x && z_last && score && n_exceed && flags;
+  if constexpr (Ep::kTrack) {
+    KRCA_CHECK_ARG(ea.gap >= 0 && ea.min_count >= 1, "%s: gap=%d must be >= 0, min_count=%d >= 1", fn, ea.gap,
+                   ea.min_count);
+    const TimelineOut& o = ea.out;
+    outs = outs && o.onset && o.last && o.count && o.peak && o.lead && o.n_metrics;
+  }
+  if (P == 0) return KRCA_OK;
+  KRCA_CHECK_ARG(outs, "%s: null pointer", fn);
+  const int64_t S = P * (int64_t)M;
+  KRCA_CHECK_ARG(S < (int64_t(1) << 32), "%s: P*M must be < 2^32", fn);
+  const double thr2 = (double)z_thr * (double)z_thr;
+  const dim3 grid((unsigned)krca::ceil_div(S, 256));
+  const ScoreCall c{x, S, T, W, M, thr2, z_last, score, n_exceed, flags, grid, krca::as_stream(stream)};
+  const int variant = krca_rolling_score_variant(P, M, T, W);
+  switch (W) {  // the cases are pipe_window()'s
+    case 60: launch_window<60, Ep>(variant, c, ea); break;
+    case 30: launch_window<30, Ep>(variant, c, ea); break;
+    case 20: launch_window<20, Ep>(variant, c, ea); break;
+    case 15: launch_window<15, Ep>(variant, c, ea); break;
+    case 10: launch_window<10, Ep>(variant, c, ea); break;
+    default: launch_reread<Ep>(c, ea);
+  }
+  KRCA_LAUNCH_CHECK();
+  return KRCA_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -668,140 +605,26 @@ int krca_usage_flags(const float* usage, int64_t P, uint8_t* flags, void* stream
 }
 
 int krca_rolling_score_variant(int64_t P, int32_t M, int32_t T, int32_t W) {
-  const krca::Tuning& tu = krca::tuning();
-  const int64_t S = P * (int64_t)M;
+  const int impl = krca::tuning().score_impl;  // tests force KRCA_SCORE_RING / KRCA_SCORE_PIPE_ROWS at small shapes
   if (!pipe_window(W)) return KRCA_SCORE_REREAD;
-  if (tu.score_impl == KRCA_SCORE_PIPE_ROWS && T > W) return KRCA_SCORE_PIPE_ROWS;  // A/B: forced
-  if (tu.score_impl == KRCA_SCORE_LDS && T > W && W == 60 && S % 4 == 0) return KRCA_SCORE_LDS;  // A/B
-  if (tu.score_impl == 0 && T > W) {
-    return S * 4 * rows_per_chunk(W) < (int64_t(1) << 31) ? KRCA_SCORE_PIPE : KRCA_SCORE_PIPE_ROWS;
-  }
-  return tu.score_impl == 2 && S * 4 * W < (int64_t(1) << 31) ? KRCA_SCORE_RING_BUF : KRCA_SCORE_RING;
+  if (T <= W || impl == KRCA_SCORE_RING) return KRCA_SCORE_RING;
+  if (impl == KRCA_SCORE_PIPE_ROWS) return KRCA_SCORE_PIPE_ROWS;
+  return P * (int64_t)M * 4 * rows_per_chunk(W) < (int64_t(1) << 31) ? KRCA_SCORE_PIPE : KRCA_SCORE_PIPE_ROWS;
 }
 
 int krca_rolling_score(const float* x, int64_t P, int32_t M, int32_t T, int32_t W, float z_thr, float* z_last,
                        float* score, int32_t* n_exceed, uint8_t* flags, void* stream) {
-  KRCA_CHECK_ARG(P >= 0 && T >= 0 && W >= 1, "krca_rolling_score: bad sizes P=%lld T=%d W=%d", (long long)P, T, W);
-  KRCA_CHECK_ARG(M >= 1 && M <= 64 && (M & (M - 1)) == 0, "krca_rolling_score: M=%d must be a power of two <= 64", M);
-  if (P == 0) return KRCA_OK;
-  KRCA_CHECK_ARG(x && z_last && score && n_exceed && flags, "krca_rolling_score: null pointer");
-  const int64_t S = P * (int64_t)M;
-  KRCA_CHECK_ARG(S < (int64_t(1) << 32), "krca_rolling_score: P*M must be < 2^32");
-  const double thr2 = (double)z_thr * (double)z_thr;
-  const dim3 grid((unsigned)krca::ceil_div(S, 256)), block(256);
-  hipStream_t st = krca::as_stream(stream);
-  // the metric stream is read once: non-temporal loads (cache policy nt) by default, 6.17 -> 6.61 TB/s
-  // at C4 (tools/score_ab.py); KRCA_SCORE_NT=0 restores the default policy
-  const bool nt = krca::tuning().score_nt != 0;
-  const int chunk = rows_per_chunk(W);
-  const int variant = krca_rolling_score_variant(P, M, T, W);
-#define KRCA_PIPE_AS(WV, CV, ROWS)                                                                               \
-  if (nt)                                                                                                        \
-    hipLaunchKernelGGL((rolling_score_pipe<WV, CV, 2, ROWS>), grid, block, 0, st, x, S, T, M, thr2, z_last, score, \
-                       n_exceed, flags, NoEpisodes::Args{});                                                     \
-  else                                                                                                           \
-    hipLaunchKernelGGL((rolling_score_pipe<WV, CV, 0, ROWS>), grid, block, 0, st, x, S, T, M, thr2, z_last, score, \
-                       n_exceed, flags, NoEpisodes::Args{});
-#define KRCA_PIPE(WV, CV)                                    \
-  if (variant == KRCA_SCORE_PIPE) { KRCA_PIPE_AS(WV, CV, SpanRows) } \
-  else { KRCA_PIPE_AS(WV, CV, BlockRows) }
-#define KRCA_RING(WV)                                                                                         \
-  if (variant == KRCA_SCORE_RING_BUF)                                                                         \
-    hipLaunchKernelGGL(rolling_score_ring_buf<WV>, grid, block, 0, st, x, S, T, M, thr2, z_last, score,        \
-                       n_exceed, flags);                                                                       \
-  else                                                                                                         \
-    hipLaunchKernelGGL(rolling_score_ring<WV>, grid, block, 0, st, x, S, T, M, thr2, z_last, score, n_exceed,  \
-                       flags);
-  const bool pipe = variant == KRCA_SCORE_PIPE || variant == KRCA_SCORE_PIPE_ROWS;
-  if (variant == KRCA_SCORE_LDS) {  // W = 60, C = 20 only
-    if (nt)
-      hipLaunchKernelGGL((rolling_score_lds<60, 20, 2>), grid, block, 0, st, x, S, T, M, thr2, z_last, score, n_exceed,
-                         flags);
-    else
-      hipLaunchKernelGGL((rolling_score_lds<60, 20, 0>), grid, block, 0, st, x, S, T, M, thr2, z_last, score, n_exceed,
-                         flags);
-  } else switch (W) {
-    case 60:
-      if (pipe && chunk == 10) { KRCA_PIPE(60, 10) }
-      else if (pipe && chunk == 12) { KRCA_PIPE(60, 12) }
-      else if (pipe && chunk == 15) { KRCA_PIPE(60, 15) }
-      else if (pipe && chunk == 30) { KRCA_PIPE(60, 30) }
-      else if (pipe) { KRCA_PIPE(60, 20) }
-      else { KRCA_RING(60) }
-      break;
-    case 30:
-      if (pipe) { KRCA_PIPE(30, 15) }
-      else { KRCA_RING(30) }
-      break;
-    case 20:
-      if (pipe) { KRCA_PIPE(20, 10) }
-      else { KRCA_RING(20) }
-      break;
-    case 15:
-      if (pipe) { KRCA_PIPE(15, 15) }
-      else { KRCA_RING(15) }
-      break;
-    case 10:
-      if (pipe) { KRCA_PIPE(10, 10) }
-      else { KRCA_RING(10) }
-      break;
-    default:
-      hipLaunchKernelGGL(rolling_score_reread<NoEpisodes>, grid, block, 0, st, x, S, T, W, M, thr2, z_last, score,
-                         n_exceed, flags, NoEpisodes::Args{});
-  }
-#undef KRCA_PIPE
-#undef KRCA_PIPE_AS
-#undef KRCA_RING
-  KRCA_LAUNCH_CHECK();
-  return KRCA_OK;
+  return launch_score<NoEpisodes>("krca_rolling_score", x, P, M, T, W, z_thr, z_last, score, n_exceed, flags,
+                                  NoEpisodes::Args{}, stream);
 }
 
 int krca_rolling_timeline(const float* x, int64_t P, int32_t M, int32_t T, int32_t W, float z_thr, int32_t gap,
                           int32_t min_count, float* z_last, float* score, int32_t* n_exceed, uint8_t* flags,
                           int32_t* onset, int32_t* last, int32_t* count, float* peak, int8_t* lead,
                           uint8_t* n_metrics, void* stream) {
-  KRCA_CHECK_ARG(P >= 0 && T >= 0 && W >= 1, "krca_rolling_timeline: bad sizes P=%lld T=%d W=%d", (long long)P, T, W);
-  KRCA_CHECK_ARG(M >= 1 && M <= 64 && (M & (M - 1)) == 0, "krca_rolling_timeline: M=%d must be a power of two <= 64",
-                 M);
-  KRCA_CHECK_ARG(gap >= 0 && min_count >= 1, "krca_rolling_timeline: gap=%d must be >= 0, min_count=%d >= 1", gap,
-                 min_count);
-  if (P == 0) return KRCA_OK;
-  KRCA_CHECK_ARG(x && z_last && score && n_exceed && flags && onset && last && count && peak && lead && n_metrics,
-                 "krca_rolling_timeline: null pointer");
-  const int64_t S = P * (int64_t)M;
-  KRCA_CHECK_ARG(S < (int64_t(1) << 32), "krca_rolling_timeline: P*M must be < 2^32");
-  const double thr2 = (double)z_thr * (double)z_thr;
-  const dim3 grid((unsigned)krca::ceil_div(S, 256)), block(256);
-  hipStream_t st = krca::as_stream(stream);
-  const bool nt = krca::tuning().score_nt != 0;
   const Episodes::Args tl{gap, min_count, TimelineOut{onset, last, count, peak, lead, n_metrics}};
-  // the pipelined kernel wherever krca_rolling_score runs one (one chunk size per window: the W = 60
-  // chunk knob is the scorer's A/B), the re-reading form everywhere else (any W, T <= W, forced A/B
-  // variants)
-  const int variant = krca_rolling_score_variant(P, M, T, W);
-  const bool pipe = variant == KRCA_SCORE_PIPE || variant == KRCA_SCORE_PIPE_ROWS;
-  const int chunk = W == 60 ? 20 : (W == 30 ? 15 : (W == 20 ? 10 : W));
-  const bool span = variant == KRCA_SCORE_PIPE && S * 4 * chunk < (int64_t(1) << 31);
-#define KRCA_TL_AS(WV, CV, AUXV, ROWS)                                                                          \
-  hipLaunchKernelGGL((rolling_score_pipe<WV, CV, AUXV, ROWS, Episodes>), grid, block, 0, st, x, S, T, M, thr2, \
-                     z_last, score, n_exceed, flags, tl)
-#define KRCA_TL(WV, CV)                                  \
-  if (span && nt) KRCA_TL_AS(WV, CV, 2, SpanRows);       \
-  else if (span) KRCA_TL_AS(WV, CV, 0, SpanRows);        \
-  else if (nt) KRCA_TL_AS(WV, CV, 2, BlockRows);         \
-  else KRCA_TL_AS(WV, CV, 0, BlockRows)
-  if (pipe && W == 60) { KRCA_TL(60, 20); }
-  else if (pipe && W == 30) { KRCA_TL(30, 15); }
-  else if (pipe && W == 20) { KRCA_TL(20, 10); }
-  else if (pipe && W == 15) { KRCA_TL(15, 15); }
-  else if (pipe && W == 10) { KRCA_TL(10, 10); }
-  else
-    hipLaunchKernelGGL(rolling_score_reread<Episodes>, grid, block, 0, st, x, S, T, W, M, thr2, z_last, score, n_exceed,
-                       flags, tl);
-#undef KRCA_TL
-#undef KRCA_TL_AS
-  KRCA_LAUNCH_CHECK();
-  return KRCA_OK;
+  return launch_score<Episodes>("krca_rolling_timeline", x, P, M, T, W, z_thr, z_last, score, n_exceed, flags, tl,
+                                stream);
 }
 
 }  // extern "C"

@@ -90,8 +90,9 @@ def test_corr_shard_ranges_tile_aligned_and_cover():
 
 
 def test_tuning_knobs_and_score_variant():
-    """A/B knobs are read once at load and changed only through krca_tune_set; the scoring variant
-    query reports the pipelined kernel at C4 and the per-row-descriptor form past 2^31 bytes."""
+    """Knobs are read once at load and changed only through krca_tune_set; the scoring variant
+    query reports the pipelined kernel at C4 and the per-row-descriptor form past 2^31 bytes.  The
+    retired knob names are unknown, and every remaining knob starts at its documented default."""
     lib = native.load_library()
     v = ctypes.c_int32(-1)
     assert lib.krca_tune_get(b"KRCA_SCORE_IMPL", ctypes.byref(v)) == 0 and v.value == 0
@@ -101,14 +102,26 @@ def test_tuning_knobs_and_score_variant():
     assert native.SCORE_VARIANTS[lib.krca_rolling_score_variant(4_000_000, 8, 1440, 60)] == "pipe_rows"
     assert native.SCORE_VARIANTS[lib.krca_rolling_score_variant(1000, 8, 50, 60)] == "ring"    # T <= W
     assert native.SCORE_VARIANTS[lib.krca_rolling_score_variant(1000, 8, 500, 7)] == "reread"  # any W
-    with native.tune(lib, KRCA_SCORE_IMPL=2):
-        assert native.SCORE_VARIANTS[lib.krca_rolling_score_variant(1000, 8, 1440, 60)] == "ring_buf"
-    with native.tune(lib, KRCA_SCORE_IMPL=5):
-        assert native.SCORE_VARIANTS[lib.krca_rolling_score_variant(1_000_000, 8, 1440, 60)] == "lds"
-        assert native.SCORE_VARIANTS[lib.krca_rolling_score_variant(1000, 8, 500, 30)] == "ring"  # W != 60
+    with native.tune(lib, KRCA_SCORE_IMPL=1):
+        assert native.SCORE_VARIANTS[lib.krca_rolling_score_variant(1000, 8, 1440, 60)] == "ring"
+    for retired in (2, 5):  # the retired variants' codes: the default answer
+        with native.tune(lib, KRCA_SCORE_IMPL=retired):
+            assert native.SCORE_VARIANTS[lib.krca_rolling_score_variant(1000, 8, 1440, 60)] == "pipe"
     with native.tune(lib, KRCA_SCORE_IMPL=4):
         assert native.SCORE_VARIANTS[lib.krca_rolling_score_variant(1000, 8, 1440, 60)] == "pipe_rows"
     assert lib.krca_tune_get(b"KRCA_SCORE_IMPL", ctypes.byref(v)) == 0 and v.value == 0  # restored
+    for name in (b"KRCA_SCORE_CHUNK", b"KRCA_SCORE_NT", b"KRCA_GROUP_IMPL", b"KRCA_CORR_PERSIST"):
+        assert lib.krca_tune_set(name, 1) != 0, name  # retired with the kernels they selected
+        assert name in lib.krca_last_error()
+    # every remaining knob and its default (csrc/krca_common.h); the environment of the test run sets none
+    defaults = {"KRCA_SCORE_IMPL": 0, "KRCA_PPR_GRID": 0, "KRCA_PPR_DICT": 1, "KRCA_LOG_IMPL": 0, "KRCA_CORR_DEBUG": 0,
+                "KRCA_CORR_RS_GRID": 1024, "KRCA_CORR_BATCH": 0, "KRCA_CORR_AMB_TILE": -1, "KRCA_PPR_FUSE": 0,
+                "KRCA_PPR_NT": 0, "KRCA_PPR_XCD": 0, "KRCA_LOG_FUSED": 0, "KRCA_CORR_RS_GROUP": 1,
+                "KRCA_CORR_SIDE": 0, "KRCA_CORR_RS_Q16": 1, "KRCA_CORR_CAPC": 0, "KRCA_CORR_KM_EXTRA": 6,
+                "KRCA_CORR_RSG_GRID": 0, "KRCA_CORR_PROJ": 2, "KRCA_TRACE_IMPL": 0}
+    for name, want in defaults.items():
+        v.value = -12345
+        assert lib.krca_tune_get(name.encode(), ctypes.byref(v)) == 0 and v.value == want, (name, v.value)
 
 
 def test_ppr_pack_decodes_to_the_remapped_columns():

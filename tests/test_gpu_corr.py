@@ -235,9 +235,8 @@ def test_corr_batches_and_full_lists_identical(eng):
     # certificate margins may differ, the sets, values and counts not)
     # (KRCA_CORR_PROJ = 0 / 1: the grouped re-score never with the projection bound / only when the
     # main pass runs in several batches -- the default uses it always; counts must not move)
-    # (KRCA_CORR_PERSIST = 1: persistent main-pass workgroups instead of one per tile)
     for knob, val in (("KRCA_CORR_RSG_GRID", 256), ("KRCA_CORR_KM_EXTRA", 2), ("KRCA_CORR_PROJ", 0),
-                      ("KRCA_CORR_PROJ", 1), ("KRCA_CORR_PERSIST", 1)):
+                      ("KRCA_CORR_PROJ", 1)):
         with native.tune(lib, **{knob: val}):
             got = eng.corr_topk(x, k=k, tau=TAU)
         for key in ("idx", "val", "count"):

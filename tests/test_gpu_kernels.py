@@ -70,25 +70,25 @@ def test_rolling_score_non_finite_samples_as_oracle(eng):
     assert np.allclose(got["score"].cpu().numpy(), ref["score"], rtol=1e-5, atol=1e-6, equal_nan=True)
 
 
-SCORE_VARIANTS = [("2", "20"), ("1", "20"), ("4", "20"), ("4", "15"), ("5", "20")] + [("0", c) for c in ("10", "12", "15", "20", "30")]
+SCORE_VARIANTS = (1, 4, 0)  # KRCA_SCORE_IMPL: plain loads and per-row descriptors forced, then the default by size
 
 
 @pytest.mark.parametrize("P,M,T,W", [(1000, 8, 1440, 60), (128, 8, 61, 60), (129, 8, 139, 60), (700, 8, 200, 30)])
 def test_rolling_score_kernel_variants_bit_exact(eng, monkeypatch, P, M, T, W):
-    """Every kernel form (W-block buffer loads, plain loads, pipelined chunks, LDS-DMA rows) = the C oracle."""
+    """Every kernel form (plain loads, pipelined chunks with per-chunk and per-row descriptors) = the C oracle."""
     x = synth.make_metrics(P, M, T, window=W, seed=P + T + 1, roots=np.arange(0, P, 9))
     ref = oracle.c_rolling_score(x.numpy(), W, 3.0)
     xd = x.cuda()
     z0 = None
-    for impl, chunk in SCORE_VARIANTS:
-        with native.tune(eng.lib, KRCA_SCORE_IMPL=int(impl), KRCA_SCORE_CHUNK=int(chunk)):
+    for impl in SCORE_VARIANTS:
+        with native.tune(eng.lib, KRCA_SCORE_IMPL=impl):
             got = eng.rolling_score(xd, window=W, z_threshold=3.0)
-        assert np.array_equal(got["n_exceed_host"], ref["n_exceed"]), (impl, chunk)
-        assert np.array_equal(got["flags"], ref["flags"]), (impl, chunk)
+        assert np.array_equal(got["n_exceed_host"], ref["n_exceed"]), impl
+        assert np.array_equal(got["flags"], ref["flags"]), impl
         z = got["z_last"].cpu().numpy()
-        assert np.allclose(z, ref["z_last"], rtol=1e-5, atol=1e-6), (impl, chunk)
+        assert np.allclose(z, ref["z_last"], rtol=1e-5, atol=1e-6), impl
         z0 = z if z0 is None else z0
-        assert np.array_equal(z, z0), (impl, chunk)                       # same arithmetic -> same bits
+        assert np.array_equal(z, z0), impl                                # same arithmetic -> same bits
 
 
 def test_rolling_score_deterministic_and_planted_roots(eng):

@@ -72,10 +72,8 @@ def test_timeline_per_row_descriptors(eng):
     with native.tune(eng.lib, KRCA_SCORE_IMPL=4):
         check_timeline(eng, x, 60, 3.0, 3, 3, "pipe_rows")
         check_timeline(eng, C.dyadic_metrics(37, 8, 61, 30, seed=5), 30, 3.0, 3, 3, "pipe_rows")
-    with native.tune(eng.lib, KRCA_SCORE_IMPL=2):  # a variant with no timeline form: the re-reading kernel
-        check_timeline(eng, x, 60, 3.0, 3, 3, "ring_buf")
-    with native.tune(eng.lib, KRCA_SCORE_NT=0):
-        check_timeline(eng, x, 60, 3.0, 3, 3, "pipe")
+    with native.tune(eng.lib, KRCA_SCORE_IMPL=1):  # a variant with no timeline form: the re-reading kernel
+        check_timeline(eng, x, 60, 3.0, 3, 3, "ring")
 
 
 def test_timeline_hand_fixture(eng):

@@ -13,10 +13,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "kubernetes-rca-system_amd"))
 
-VARIANTS = [("ring_buf", {"KRCA_SCORE_IMPL": 2}), ("ring", {"KRCA_SCORE_IMPL": 1})] + [
-    (f"pipe_c{c}", {"KRCA_SCORE_IMPL": 0, "KRCA_SCORE_CHUNK": c}) for c in (10, 12, 15, 20, 30)] + [
-    ("pipe_c20_default_policy", {"KRCA_SCORE_IMPL": 0, "KRCA_SCORE_CHUNK": 20, "KRCA_SCORE_NT": 0}),
-    ("lds", {"KRCA_SCORE_IMPL": 5}), ("lds_default_policy", {"KRCA_SCORE_IMPL": 5, "KRCA_SCORE_NT": 0})]
+VARIANTS = [("pipe", {"KRCA_SCORE_IMPL": 0}), ("ring", {"KRCA_SCORE_IMPL": 1}), ("pipe_rows", {"KRCA_SCORE_IMPL": 4})]
 
 
 def main():
@@ -34,13 +31,12 @@ def main():
     nbytes = 4 * a.pods * 8 * a.tsteps + 4 * a.pods * 8 + 9 * a.pods
     ref = None
     res = []
-    defaults = {"KRCA_SCORE_IMPL": 0, "KRCA_SCORE_CHUNK": 20, "KRCA_SCORE_NT": 1}
     for rnd in range(a.rounds):
         for name, knobs in VARIANTS:
             if a.only and name not in a.only.split(","):
                 continue
             # knobs are read once at library load: set them through krca_tune_set
-            with native.tune(eng.lib, **dict(defaults, **knobs)):
+            with native.tune(eng.lib, **knobs):
                 variant = native.SCORE_VARIANTS[eng.lib.krca_rolling_score_variant(a.pods, 8, a.tsteps, 60)]
                 o = eng.rolling_score_device(x)
                 torch.cuda.synchronize()
