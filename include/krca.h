@@ -49,7 +49,7 @@ int krca_version(void);
 const char* krca_last_error(void);
 int krca_device_count(int* n_host);
 
-/* Kernel-development switches and test hooks: KRCA_SCORE_IMPL, KRCA_PPR_GRID, KRCA_PPR_DICT, KRCA_LOG_IMPL, KRCA_CORR_DEBUG,
+/* Kernel-development switches and test hooks: KRCA_SCORE_IMPL, KRCA_PPR_GRID, KRCA_PPR_DICT, KRCA_CORR_DEBUG,
  * KRCA_CORR_RS_GRID, KRCA_CORR_BATCH, KRCA_CORR_AMB_TILE, KRCA_PPR_FUSE, KRCA_PPR_NT, KRCA_PPR_XCD, KRCA_LOG_FUSED,
  * KRCA_CORR_RS_GROUP, KRCA_CORR_SIDE, KRCA_CORR_RS_Q16, KRCA_CORR_CAPC, KRCA_CORR_KM_EXTRA, KRCA_CORR_RSG_GRID,
  * KRCA_CORR_PROJ, KRCA_TRACE_IMPL (meanings and defaults: csrc/krca_common.h).  Initialised once from the

@@ -29,7 +29,6 @@ const NamedKnob kKnobs[] = {
     {"KRCA_SCORE_IMPL", &Tuning::score_impl, 0},
     {"KRCA_PPR_GRID", &Tuning::ppr_grid, 0},
     {"KRCA_PPR_DICT", &Tuning::ppr_dict, 1},
-    {"KRCA_LOG_IMPL", &Tuning::log_impl, 0},
     {"KRCA_CORR_DEBUG", &Tuning::corr_debug, 0},
     {"KRCA_CORR_RS_GRID", &Tuning::corr_rs_grid, 1024},
     {"KRCA_CORR_BATCH", &Tuning::corr_batch, 0},

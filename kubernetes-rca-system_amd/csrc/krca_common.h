@@ -94,8 +94,6 @@ struct Tuning {
                     // descriptors (the small-shape test hooks of those paths); any other value as 0
   int ppr_grid;     // KRCA_PPR_GRID [0]: persistent PageRank grid (0 = occupancy API)
   int ppr_dict;     // KRCA_PPR_DICT [1]: krca_ppr_pack builds dictionary blocks (0 = all direct)
-  int log_impl;     // KRCA_LOG_IMPL [0]: krca_log_match's walk: 0 line index + DFA lanes, 1 chunk-lane single pass,
-                    // 2 line index + the code-point walk log_dfa_window
   int corr_debug;   // KRCA_CORR_DEBUG [0]: profiling aid (results wrong when != 0)
   int corr_rs_grid; // KRCA_CORR_RS_GRID [1024]: workgroups of the ambiguous-pair re-score (a multiple of 8)
   int corr_batch;   // KRCA_CORR_BATCH [0]: super-tiles per main-pass batch (0 = 8192)

@@ -21,9 +21,8 @@
 //   log_hist          lane per container (or a wave for a large one): 13 counts, the first three
 //                     example lines per bin marked in the line masks, no atomics.
 // A/B paths (tests require identical outputs): KRCA_LOG_FUSED = 1 / 2, log_index_match walking the
-// DFA inside the index pass from the LDS-resident tile (+ the LOOK bytes after it, for its last line);
-// KRCA_LOG_IMPL = 1, the chunk-lane log_match; = 2, the round-1 walk log_dfa_window.  When the
-// caller's line arrays are too small, krca_log_match finishes from the index in the workspace.
+// DFA inside the index pass from the LDS-resident tile (+ the LOOK bytes after it, for its last line).
+// When the caller's line arrays are too small, krca_log_match finishes from the index in the workspace.
 #include <stdint.h>
 #include <cstdlib>
 
@@ -79,47 +78,6 @@ struct Bytes {
   }
 };
 
-__device__ __forceinline__ bool is_ascii_sep(uint32_t b) {
-  return b == 0x0A || b == 0x0B || b == 0x0C || b == 0x0D || b == 0x1C || b == 0x1D || b == 0x1E;
-}
-
-// a separator ends at p-1, given bytes b3 b2 b1 = text[p-3..p-1] (0 outside the container)
-// and b0 = text[p] (0 at the container end): position p starts a line (if inside the container)
-__device__ __forceinline__ bool sep_before(uint32_t b3, uint32_t b2, uint32_t b1, uint32_t b0) {
-  if (b1 == 0x0D) return b0 != 0x0A;
-  if (b1 == 0x0A || b1 == 0x0B || b1 == 0x0C || b1 == 0x1C || b1 == 0x1D || b1 == 0x1E) return true;
-  if (b2 == 0xC2 && b1 == 0x85) return true;
-  return b3 == 0xE2 && b2 == 0x80 && (b1 == 0xA8 || b1 == 0xA9);
-}
-
-// The container window of a lane: the current container d and the next boundaries off[d .. d+4]
-// held in registers, refilled one load ahead, so crossing a container boundary (a ~184-byte
-// container per 256-byte chunk at C5) does not wait on a dependent global load.
-struct DocWin {
-  const int64_t* off;
-  int64_t D, d;
-  int64_t b[5];
-  __device__ __forceinline__ void load(const int64_t* o, int64_t nd, int64_t d0) {
-    off = o;
-    D = nd;
-    d = d0;
-#pragma unroll
-    for (int i = 0; i < 5; ++i) b[i] = d0 + i <= nd ? o[d0 + i] : INT64_MAX;
-  }
-  // move to the container holding byte p (skipping empty containers sitting at p)
-  __device__ __forceinline__ void advance(int64_t p) {
-    while (d + 1 < D && b[1] <= p) {
-      ++d;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) b[i] = b[i + 1];
-      b[4] = d + 4 <= D ? off[d + 4] : INT64_MAX;
-    }
-  }
-};
-
-// byte k (0..3) of a little-endian word
-__device__ __forceinline__ uint32_t byte_of(uint32_t w, int k) { return (w >> (8 * k)) & 0xFFu; }
-
 // chunk -> container holding its first byte: one thread per container writes the chunks that start
 // inside it (every chunk start lies in exactly one non-empty container), so no chunk searches.
 // (Line starts at container first bytes are counted by log_count from its tile bitmap: every
@@ -160,8 +118,8 @@ __device__ __forceinline__ uint32_t swar_range(uint32_t x, uint32_t lo, uint32_t
   return ge & ~gt & ~x & 0x80808080u;
 }
 
-// line starts at the 4 byte positions of word w (sep_before of each, raw bytes), given the word
-// before it; high bit per byte
+// line starts at the 4 byte positions of word w (a separator ends right before each, raw bytes),
+// given the word before it; high bit per byte
 __device__ __forceinline__ uint32_t sep_flags(uint32_t wprev, uint32_t w) {
   const uint32_t B1 = __builtin_amdgcn_alignbit(w, wprev, 24);  // text[p-1] at byte k
   uint32_t f = (swar_range(B1, 0x0A, 0x0D) | swar_range(B1, 0x1C, 0x1E)) & ~(swar_eq(B1, 0x0D) & swar_eq(w, 0x0A));
@@ -308,7 +266,7 @@ __global__ __launch_bounds__(1024) void log_scan(int64_t* __restrict__ tile, int
   }
 }
 
-// ---- phase 3: DFA per chunk ----------------------------------------------------------------
+// ---- the code-point DFA of log_dfa_long -----------------------------------------------------
 struct DfaLds {
   uint16_t trans[KRCA_DFA_NSTATE * KRCA_DFA_NSYM];
   uint16_t out[KRCA_DFA_NSTATE];
@@ -352,199 +310,7 @@ __device__ __forceinline__ int64_t cp_align(Bytes& B, int64_t p, int64_t lim) {
   return p;
 }
 
-__global__ __launch_bounds__(TPB) void log_match(const uint8_t* __restrict__ text, int64_t nbytes,
-                                                 const int64_t* __restrict__ doc_off, int64_t D,
-                                                 const int32_t* __restrict__ chunk_doc,
-                                                 const int32_t* __restrict__ chunk_cnt,
-                                                 const int64_t* __restrict__ tile_base, int64_t ntiles, int64_t L,
-                                                 int64_t* __restrict__ line_start, int64_t* __restrict__ line_end,
-                                                 uint32_t* __restrict__ line_mask, int64_t* __restrict__ chunk_line0) {
-  __shared__ DfaLds dfa;
-  __shared__ int64_t s_scan[TPB];
-  __shared__ int64_t s_first_id[TPB];
-  __shared__ uint32_t s_first_mask[TPB];
-  __shared__ int32_t s_first_closed[TPB];
-  for (int i = threadIdx.x; i < KRCA_DFA_NSTATE * KRCA_DFA_NSYM; i += TPB) dfa.trans[i] = krca_dfa_trans[i];
-  for (int i = threadIdx.x; i < KRCA_DFA_NSTATE; i += TPB) dfa.out[i] = krca_dfa_out[i];
-  for (int i = threadIdx.x; i < 128; i += TPB) dfa.ascii[i] = krca_dfa_ascii_sym[i];
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-
-  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-    // exclusive scan of the tile's chunk counts -> first line id of this lane's chunk
-    const int64_t g = tile * TPB + threadIdx.x;
-    const int64_t v = chunk_cnt[g];
-    int64_t x = v;
-    for (int off = 1; off < 64; off <<= 1) {
-      const int64_t y = (int64_t)__shfl_up((long long)x, off, 64);
-      if (lane >= off) x += y;
-    }
-    __syncthreads();  // protects s_scan / s_first_* of the previous tile and the DFA fill
-    if (lane == 63) s_scan[wid] = x;
-    __syncthreads();
-    int64_t base = tile_base[tile];
-    for (int w = 0; w < wid; ++w) base += s_scan[w];
-    base += x - v;
-    chunk_line0[g] = base;  // first line id of the chunk (narrows log_hist's search)
-
-    const int64_t c0 = g * CH;
-    int64_t first_id = -1;
-    uint32_t first_mask = 0;
-    int32_t first_closed = 0;
-    int64_t tail_id = -1;  // a line this lane opened and did not close
-    uint32_t tail_mask = 0;
-    if (c0 < nbytes) {
-      const int64_t c1 = min(c0 + CH, nbytes);
-      Bytes B;
-      B.init(text, nbytes);
-      DocWin dw;
-      dw.load(doc_off, D, min(max((int64_t)chunk_doc[g], (int64_t)0), D - 1));
-      int64_t dstart = dw.b[0], dend = dw.b[1];
-      const int64_t p0 = cp_align(B, c0, dend);  // first code point starting in this chunk
-      int64_t cur = base - 1;  // id of the open line (lines before this chunk: base)
-      bool open = false, own = false, after_sep = false, prev_cr = false;
-      uint32_t st = 0, mask = 0;
-      if (p0 < dend && p0 > dstart) {
-        const uint32_t b1 = B.at(p0 - 1);
-        const uint32_t b2 = p0 - 2 >= dstart ? B.at(p0 - 2) : 0;
-        const uint32_t b3 = p0 - 3 >= dstart ? B.at(p0 - 3) : 0;
-        const uint32_t b0 = B.at(p0);
-        if (b1 == 0x0D) {
-          after_sep = true;
-          prev_cr = true;
-        } else if (sep_before(b3, b2, b1, b0)) {
-          after_sep = true;
-        } else {
-          open = true;  // continuation of line `cur` opened by an earlier chunk
-          // DFA warm-up over the preceding <= WARM code points of this line
-          int64_t k = p0;
-          int seen = 0;
-          while (k > dstart && seen < WARM) {
-            const uint32_t b = B.at(k - 1);
-            if (is_ascii_sep(b)) break;
-            --k;
-            if ((b & 0xC0) != 0x80) ++seen;
-          }
-          while (k < p0) {
-            uint32_t cp;
-            const int len = decode(B, k, cp);
-            const uint32_t sym = cp_symbol(dfa, cp);
-            st = sym == KRCA_DFA_SEP ? 0u : dfa.trans[st * KRCA_DFA_NSYM + sym];
-            k += len;
-          }
-          // pieces before p0 belong to earlier chunks; only the state is carried over
-        }
-      }
-      int64_t p = p0;
-      // process code points starting in [p0, c1) (the last one may extend past c1)
-      while (p < c1) {
-        if (p >= dend) {  // container end: close its open last line, enter the next container
-          if (open) {
-            if (cur < L) line_end[cur] = dend;
-            if (own && cur < L) line_mask[cur] = mask;
-            else {
-              first_id = cur;
-              first_mask = mask;
-              first_closed = 1;
-            }
-            open = false;
-          }
-          dw.advance(p);
-          dstart = dw.b[0];
-          dend = dw.b[1];
-          after_sep = false;
-          prev_cr = false;
-        }
-        uint32_t cp;
-        const int len = decode(B, p, cp);
-        if (p == dstart || after_sep) {
-          if (after_sep && prev_cr && cp == 0x0A) {  // second byte of "\r\n"
-            prev_cr = false;
-            p += len;
-            continue;
-          }
-          ++cur;  // a new line starts here
-          if (cur < L) line_start[cur] = p;
-          open = true;
-          own = true;
-          after_sep = false;
-          prev_cr = false;
-          st = 0;
-          mask = 0;
-        }
-        const uint32_t sym = cp_symbol(dfa, cp);
-        if (sym == KRCA_DFA_SEP) {
-          if (open) {
-            if (cur < L) line_end[cur] = p;
-            if (own && cur < L) line_mask[cur] = mask;
-            else {
-              first_id = cur;
-              first_mask = mask;
-              first_closed = 1;
-            }
-          }
-          open = false;
-          after_sep = true;
-          prev_cr = cp == 0x0D;
-          st = 0;
-        } else {
-          st = dfa.trans[st * KRCA_DFA_NSYM + sym];
-          mask |= dfa.out[st];
-        }
-        p += len;
-      }
-      if (open && p >= dend) {  // the container ends exactly at the chunk end
-        if (cur < L) line_end[cur] = dend;
-        if (own && cur < L) line_mask[cur] = mask;
-        else {
-          first_id = cur;
-          first_mask = mask;
-          first_closed = 1;
-        }
-        open = false;
-      }
-      if (open) {
-        if (own) {
-          tail_id = cur;
-          tail_mask = mask;
-        } else {  // the line crosses this whole chunk
-          first_id = cur;
-          first_mask = mask;
-          first_closed = 0;
-        }
-      }
-    }
-    s_first_id[threadIdx.x] = first_id;
-    s_first_mask[threadIdx.x] = first_mask;
-    s_first_closed[threadIdx.x] = first_closed;
-    __syncthreads();
-    // owners of open lines collect the continuation pieces of the following lanes
-    if (tail_id >= 0 && tail_id < L) {
-      uint32_t m = tail_mask;
-      bool closed = false;
-      for (int j = threadIdx.x + 1; j < TPB && s_first_id[j] == tail_id; ++j) {
-        m |= s_first_mask[j];
-        if (s_first_closed[j]) {
-          closed = true;
-          break;
-        }
-      }
-      if (closed) line_mask[tail_id] = m;
-      else atomicOr(&line_mask[tail_id], m);  // continues into the next tile
-    }
-    // lane 0 finishes a line opened in an earlier tile
-    if (threadIdx.x == 0 && s_first_id[0] >= 0 && s_first_id[0] < L) {
-      const int64_t id = s_first_id[0];
-      uint32_t m = 0;
-      for (int j = 0; j < TPB && s_first_id[j] == id; ++j) {
-        m |= s_first_mask[j];
-        if (s_first_closed[j]) break;
-      }
-      atomicOr(&line_mask[id], m);
-    }
-  }
-}
-
-// ---- phase 3 (default, KRCA_LOG_IMPL != 1): line index, then a DFA lane per line ---------------
+// ---- phase 3: line index, then a DFA lane per line ---------------------------------------------
 // log_lines  re-streams the text like log_count (coalesced 16-byte pieces, SWAR separator tests)
 //            plus the container starts of each piece, numbers every line start from the chunk
 //            bases and writes line_start[id] and line_end[id-1] (the previous line ends at the
@@ -553,7 +319,7 @@ __global__ __launch_bounds__(TPB) void log_match(const uint8_t* __restrict__ tex
 //            per-byte loop is just UTF-8 decode + DFA step + mask OR; lines longer than LONG_LINE
 //            are queued for
 // log_dfa_long  one wave per long line: 64 segments, each warmed up over the <= 23 code points
-//            before it (as log_match's chunks), OR-reduced across the wave.
+//            before it, OR-reduced across the wave.
 constexpr int LONG_LINE = 1024;
 
 // bytes of the separator that ends right before p (0: none), from the raw bytes before p; p1_cs:
@@ -707,37 +473,17 @@ __device__ __forceinline__ uint64_t lb_load(const unsigned long long* p) {
   return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// high bits of sep_len's length-1 / length-2 / length-3 cases at the 4 positions of word w (given
-// the word before it), as 4-bit masks; cs4 = container first byte at p-1 for each position
-__device__ __forceinline__ void sep_planes(uint32_t wprev, uint32_t w, uint32_t cs4, uint32_t& l0, uint32_t& l1) {
-  const uint32_t B1 = __builtin_amdgcn_alignbit(w, wprev, 24);  // text[p-1] at byte k
-  const uint32_t B2 = __builtin_amdgcn_alignbit(w, wprev, 16);
-  const uint32_t nl = high_bits4(swar_eq(B1, 0x0A));
-  const uint32_t crlf = nl & high_bits4(swar_eq(B2, 0x0D)) & ~cs4;
-  uint32_t one = (nl & ~crlf) | high_bits4(swar_range(B1, 0x0B, 0x0D) | swar_range(B1, 0x1C, 0x1E));
-  uint32_t two = crlf;
-  if ((w | wprev) & 0x80808080u) {  // U+0085 (2 bytes), U+2028 / U+2029 (3 bytes)
-    const uint32_t B3 = __builtin_amdgcn_alignbit(w, wprev, 8);
-    two |= high_bits4(swar_eq(B2, 0xC2) & swar_eq(B1, 0x85));
-    const uint32_t three = high_bits4(swar_eq(B3, 0xE2) & swar_eq(B2, 0x80) & (swar_eq(B1, 0xA8) | swar_eq(B1, 0xA9)));
-    one |= three;
-    two |= three;
-  }
-  l0 = one;
-  l1 = two;
-}
-
 // high bits of the 4 bytes of f -> bits 0..3 (one multiply: the four partial products land on
 // distinct bits, no carries)
 __device__ __forceinline__ uint32_t gather4(uint32_t f) { return ((f & 0x80808080u) * 0x00204081u) >> 28; }
 
 // Line starts S and the separator-length planes L0 (lengths 1, 3) / L1 (lengths 2, 3) at the 16
-// positions q..q+15 of a piece, sep_before / sep_len restated on 16-bit masks: the byte tests run
+// positions q..q+15 of a piece, sep_flags / sep_len restated on 16-bit masks: the byte tests run
 // once per byte of the piece (T(k) = test of byte q+k; bit -1 = byte q-1 from wp) and the "byte
 // before p" forms are those masks shifted by one -- instead of re-testing the shifted words
-// (sep_flags + sep_planes: ~390 vector instructions per piece and wave).  cs = container first
-// bytes at q-1+k (bit k): a "\r" there belongs to the previous container, so "\r\n" is not one
-// separator across it.
+// (sep_flags, and as much again for the length planes: ~390 vector instructions per piece and
+// wave).  cs = container first bytes at q-1+k (bit k): a "\r" there belongs to the previous
+// container, so "\r\n" is not one separator across it.
 // Common case first (round 6): a piece whose bytes, and the two before it, hold no separator but
 // "\n" and no byte >= 0x80 has S = L0 = the positions after its "\n"s, L1 = 0 -- the other tests'
 // gathers and the "\r\n" logic are skipped (a wave takes the full path only when one of its lanes
@@ -1008,11 +754,6 @@ __device__ __forceinline__ void fill_out(uint16_t* out) {
   __syncthreads();
 }
 
-__device__ __forceinline__ uint32_t dfa_row_entry(int i) {
-  const uint32_t t = krca_dfa_trans[i];
-  return t * KRCA_DFA_NSYM | (krca_dfa_out[t] ? kAcc : 0u);
-}
-
 __device__ __forceinline__ void dfa_load(DfaLds& dfa) {
   for (int i = threadIdx.x; i < 128; i += blockDim.x) dfa.ascii[i] = krca_dfa_ascii_sym[i];
   fill_out(dfa.out);
@@ -1026,49 +767,11 @@ __device__ __forceinline__ void dfa_load(DfaLds& dfa) {
 // SIMD to hide the walk's dependent LDS round trips (256-lane groups left it at 4).
 constexpr int DFA_TPB = 512;
 
-__global__ __launch_bounds__(DFA_TPB) void log_dfa_window(const uint8_t* __restrict__ text, int64_t nbytes, int64_t L,
-                                                   const int64_t* __restrict__ line_start,
-                                                   const int64_t* __restrict__ line_end, uint32_t* __restrict__ line_mask,
-                                                   int32_t* __restrict__ long_q, int32_t* __restrict__ n_long) {
-  __shared__ DfaLds dfa;
-  dfa_load(dfa);
-  Bytes B;
-  B.init(text, nbytes);
-  for (int64_t l = (int64_t)blockIdx.x * DFA_TPB + threadIdx.x; l < L; l += (int64_t)gridDim.x * DFA_TPB) {
-    const int64_t s = line_start[l], e = line_end[l];
-    if (e - s > LONG_LINE) {
-      long_q[atomicAdd(n_long, 1)] = (int32_t)l;  // a wave per long line (log_dfa_long)
-      continue;
-    }
-    uint32_t row = 0, mask = 0;
-    if (s < e) {
-      // software-pipelined walk: the symbol of the next code point is looked up while the
-      // transition of the current one is in flight (one LDS round trip per byte, not two)
-      uint32_t cp;
-      int len = decode(B, s, cp);
-      uint32_t sym = cp_symbol(dfa, cp);
-      for (int64_t p = s;;) {
-        const uint32_t t = dfa.trans[row + sym];
-        p += len;
-        const bool more = p < e;
-        if (more) {
-          len = decode(B, p, cp);
-          sym = cp_symbol(dfa, cp);
-        }
-        row = t & (kAcc - 1);
-        if (__builtin_expect((t & kAcc) != 0, 0)) mask |= dfa.out[row / KRCA_DFA_NSYM];
-        if (!more) break;
-      }
-    }
-    line_mask[l] = mask;
-  }
-}
-
 // ---- log_dfa: the walk, four bytes per word and sixteen per block --------------------------
-// The round-1 walk (log_dfa_window, kept for A/B) spent ~20 instructions per byte on the 16-byte
-// window bookkeeping, the UTF-8 decode branches and the accept test, with a dependent global
-// refill every 16 bytes at a different iteration in each lane (the memory counter being per
-// wave, nearly every step of a wave waited on one).  This walk:
+// A walk over a 16-byte register window, a code point per step (round 1), spent ~20 instructions
+// per byte on the window bookkeeping, the UTF-8 decode branches and the accept test, with a
+// dependent global refill every 16 bytes at a different iteration in each lane (the memory counter
+// being per wave, nearly every step of a wave waited on one).  This walk:
 //  * moves every lane of a wave through its line in lockstep blocks of 16 bytes (starting at the
 //    line's 4-byte-aligned start): one buffer load per block per lane, issued a block ahead into
 //    the other half of a register ping-pong, so a wave's loads are issued together and each
@@ -1315,16 +1018,6 @@ __global__ __launch_bounds__(TPB) void log_dfa_long(const uint8_t* __restrict__ 
 }
 
 // ---- phase 4: per-container histogram + first three examples (wave per container) ----------
-__device__ __forceinline__ int64_t lower_bound_i64(const int64_t* __restrict__ a, int64_t n, int64_t key) {
-  int64_t lo = 0, hi = n;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (a[mid] < key) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
-
 // One lane per container: its first line by one binary search over line_start (the next lane's
 // result is its end), then, for a container of <= 32 lines, a private loop over the line masks;
 // larger containers are taken by the whole wave one at a time (13 ballots per 64 lines give the
@@ -2067,14 +1760,7 @@ int krca_log_match(const uint8_t* text, int64_t nbytes, const int64_t* doc_off, 
   int64_t* chunk_line0 = w.chunk_line0;
   int32_t *n_long = w.n_long, *long_q = w.long_q;
   hipStream_t st = krca::as_stream(stream);
-  const int impl = krca::tuning().log_impl;  // A/B: tests switch it with krca_tune_set
-  if (n_lines > 0 && impl == 1) {  // A/B: lane per 256-byte chunk, DFA and line logic in one pass
-    KRCA_HIP(hipMemsetAsync(line_mask, 0, n_lines * sizeof(uint32_t), st));
-    const int64_t grid = std::min<int64_t>(nt, 256 * 4);
-    hipLaunchKernelGGL(log_match, dim3((unsigned)grid), dim3(TPB), 0, st, text, nbytes, doc_off, ndocs, cdoc, chunk,
-                       tile, nt, n_lines, line_start, line_end, line_mask, chunk_line0);
-    KRCA_LAUNCH_CHECK();
-  } else if (n_lines > 0) {  // line index, then a DFA lane per line (long lines: a wave each)
+  if (n_lines > 0) {  // line offsets from the index, then a DFA lane per line (long lines: a wave each)
     KRCA_HIP(hipMemsetAsync(n_long, 0, sizeof(int32_t), st));
     hipLaunchKernelGGL(log_lines, dim3((unsigned)nt), dim3(TPB), 0, st, text, nbytes, doc_off, ndocs, cdoc, chunk, tile,
                        n_lines, line_start, line_end, chunk_line0);
@@ -2082,15 +1768,11 @@ int krca_log_match(const uint8_t* text, int64_t nbytes, const int64_t* doc_off, 
     hipLaunchKernelGGL(log_last_end, dim3(1), dim3(1), 0, st, text, nbytes, doc_off, ndocs, n_lines,
                        (const int64_t*)nullptr, (int64_t)0, line_end);
     KRCA_LAUNCH_CHECK();
-    if (impl == 2) {  // A/B: the round-1 walk (16-byte window, code point per step)
-      const int64_t grid = std::min<int64_t>(krca::ceil_div(n_lines, DFA_TPB), 256 * 4);
-      hipLaunchKernelGGL(log_dfa_window, dim3((unsigned)grid), dim3(DFA_TPB), 0, st, text, nbytes, n_lines,
-                         (const int64_t*)line_start, (const int64_t*)line_end, line_mask, long_q, n_long);
-    } else {  // persistent: the 50 KB table is filled once per workgroup, 3 workgroups per CU
-      const int64_t grid = std::min<int64_t>(krca::ceil_div(n_lines, DFA_TPB), 256 * 3);
-      hipLaunchKernelGGL(log_dfa, dim3((unsigned)grid), dim3(DFA_TPB), 0, st, text, nbytes, n_lines,
-                         (const int64_t*)nullptr, (int64_t)0, (const int64_t*)line_start, (const int64_t*)line_end, line_mask, long_q, n_long);
-    }
+    // persistent: the 50 KB table is filled once per workgroup, 3 workgroups per CU
+    const int64_t grid = std::min<int64_t>(krca::ceil_div(n_lines, DFA_TPB), 256 * 3);
+    hipLaunchKernelGGL(log_dfa, dim3((unsigned)grid), dim3(DFA_TPB), 0, st, text, nbytes, n_lines,
+                       (const int64_t*)nullptr, (int64_t)0, (const int64_t*)line_start, (const int64_t*)line_end,
+                       line_mask, long_q, n_long);
     KRCA_LAUNCH_CHECK();
     hipLaunchKernelGGL(log_dfa_long, dim3(256), dim3(TPB), 0, st, text, nbytes, (const int64_t*)line_start,
                        (const int64_t*)line_end, line_mask, (const int32_t*)long_q, (const int32_t*)n_long);

@@ -742,23 +742,16 @@ class NativeEngine:
         hist = torch.empty((D, NCAT), dtype=torch.int32, device=self.device)
         ex = torch.empty((D, NCAT, 3), dtype=torch.int32, device=self.device) if dense_examples else None
         exp = self.ptr(ex) if ex is not None else None
-        if self.lib_tuning_log_impl() != 0:  # A/B walks: the two-call protocol (index, then match)
-            nl = torch.zeros(1, dtype=torch.int64, device=self.device)
-            _check(self.lib.krca_log_index(self.ptr(text), nbytes, self.ptr(doc_off), D, self.ptr(ws), self.ptr(nl),
-                                           st), "krca_log_index")
-            L = int(nl.item())
-            cap = -1
-        else:
-            # one call (krca_log_scan) into line arrays of the capacity the last scan needed (+25 %);
-            # a larger window falls through to krca_log_match with the index the call left in ws
-            cap = max(self._log_cap, 1024)
-            ls, le, lm = (torch.empty(cap, dtype=dt, device=self.device) for dt in (torch.int64, torch.int64, torch.int32))
-            nh = c_i64(0)
-            _check(self.lib.krca_log_scan(self.ptr(text), nbytes, self.ptr(doc_off), D, self.ptr(ws), cap,
-                                          self.ptr(ls), self.ptr(le), self.ptr(lm), self.ptr(dl), self.ptr(hist),
-                                          exp, self.ptr(d0), ctypes.byref(nh), st), "krca_log_scan")
-            L = int(nh.value)
-            self._log_cap = max(self._log_cap, L + L // 4)
+        # one call (krca_log_scan) into line arrays of the capacity the last scan needed (+25 %);
+        # a larger window falls through to krca_log_match with the index the call left in ws
+        cap = max(self._log_cap, 1024)
+        ls, le, lm = (torch.empty(cap, dtype=dt, device=self.device) for dt in (torch.int64, torch.int64, torch.int32))
+        nh = c_i64(0)
+        _check(self.lib.krca_log_scan(self.ptr(text), nbytes, self.ptr(doc_off), D, self.ptr(ws), cap,
+                                      self.ptr(ls), self.ptr(le), self.ptr(lm), self.ptr(dl), self.ptr(hist),
+                                      exp, self.ptr(d0), ctypes.byref(nh), st), "krca_log_scan")
+        L = int(nh.value)
+        self._log_cap = max(self._log_cap, L + L // 4)
         if L > cap:
             ls = torch.empty(max(L, 1), dtype=torch.int64, device=self.device)
             le = torch.empty(max(L, 1), dtype=torch.int64, device=self.device)
@@ -768,11 +761,6 @@ class NativeEngine:
                                            exp, self.ptr(d0), st), "krca_log_match")
         return dict(n_lines_total=L, line_start=ls[:L], line_end=le[:L], line_mask=lm[:L], doc_lines=dl,
                     doc_line0=d0, hist=hist, examples=ex, text=text)
-
-    def lib_tuning_log_impl(self):
-        v = c_i32(0)
-        _check(self.lib.krca_tune_get(b"KRCA_LOG_IMPL", ctypes.byref(v)), "krca_tune_get", self.lib)
-        return int(v.value)
 
     # -- a13 ---------------------------------------------------------------------------------
     def template_hist_device(self, scan, defer_huge=False):

@@ -10,7 +10,7 @@ pull-CSR.
    (float64 window sums, the last W samples and the exceedance bits of the last H evaluated steps
    stay in HBM), so a window costs O(n_local*M*delta) instead of re-reading the history; its
    outputs equal krca_rolling_score over the whole series so far, bit for bit.  No communication.
-2. The window's log text of the rank's containers goes through krca_log_index / krca_log_match
+2. The window's log text of the rank's containers goes through krca_log_scan
    (13-pattern histograms per container, the reference's LogsAgent semantics,
    ref:agents/logs_agent.py:147-151) and krca_template_hash / krca_template_hist (error-template
    histograms per container).  No communication.

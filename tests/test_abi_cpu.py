@@ -114,7 +114,7 @@ def test_tuning_knobs_and_score_variant():
         assert lib.krca_tune_set(name, 1) != 0, name  # retired with the kernels they selected
         assert name in lib.krca_last_error()
     # every remaining knob and its default (csrc/krca_common.h); the environment of the test run sets none
-    defaults = {"KRCA_SCORE_IMPL": 0, "KRCA_PPR_GRID": 0, "KRCA_PPR_DICT": 1, "KRCA_LOG_IMPL": 0, "KRCA_CORR_DEBUG": 0,
+    defaults = {"KRCA_SCORE_IMPL": 0, "KRCA_PPR_GRID": 0, "KRCA_PPR_DICT": 1, "KRCA_CORR_DEBUG": 0,
                 "KRCA_CORR_RS_GRID": 1024, "KRCA_CORR_BATCH": 0, "KRCA_CORR_AMB_TILE": -1, "KRCA_PPR_FUSE": 0,
                 "KRCA_PPR_NT": 0, "KRCA_PPR_XCD": 0, "KRCA_LOG_FUSED": 0, "KRCA_CORR_RS_GROUP": 1,
                 "KRCA_CORR_SIDE": 0, "KRCA_CORR_RS_Q16": 1, "KRCA_CORR_CAPC": 0, "KRCA_CORR_KM_EXTRA": 6,

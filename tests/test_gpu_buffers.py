@@ -25,7 +25,7 @@ from krca import native, podstate, synth, tracecols
 from krca.agents.logs import pack_documents
 from krca.agents.topology import csr_from_edges
 from test_gpu_groupby import _records
-from test_gpu_kernels import _explain_graph
+from test_gpu_kernels import _explain_graph, scan_two_calls
 from test_gpu_topograph import _rand_sets
 from test_gpu_trace import _edge_case, _link_case, _stats_case
 
@@ -486,26 +486,6 @@ def _scan_one_call(e, blob, off, cap):
     return {k: host(r[k]) for k in LOG_KEYS}
 
 
-def _scan_two_calls(e, blob, off):
-    """krca_log_index, then krca_log_match into line arrays of exactly the line count."""
-    t = e.torch
-    text, offd = e.upload_blob(blob), e._dev(np.asarray(off, np.int64))
-    nbytes, D = len(blob), len(off) - 1
-    ws = e._workspace("logidx", 8 * e.lib.krca_log_index_size(nbytes))
-    nl = t.empty(1, dtype=t.int64, device=e.device)
-    native._check(e.lib.krca_log_index(e.ptr(text), nbytes, e.ptr(offd), D, e.ptr(ws), e.ptr(nl), e._stream()),
-                  "krca_log_index")
-    L = int(nl.item())
-    new = lambda dt, *shape: t.empty(shape, dtype=dt, device=e.device)  # noqa: E731
-    r = dict(line_start=new(t.int64, L), line_end=new(t.int64, L), line_mask=new(t.int32, L), doc_lines=new(t.int32, D),
-             doc_line0=new(t.int64, D), hist=new(t.int32, D, native.NCAT), examples=new(t.int32, D, native.NCAT, 3))
-    native._check(e.lib.krca_log_match(e.ptr(text), nbytes, e.ptr(offd), D, e.ptr(ws), L, e.ptr(r["line_start"]),
-                                       e.ptr(r["line_end"]), e.ptr(r["line_mask"]), e.ptr(r["doc_lines"]),
-                                       e.ptr(r["hist"]), e.ptr(r["examples"]), e.ptr(r["doc_line0"]), e._stream()),
-                  "krca_log_match")
-    return {k: host(r[k]) for k in LOG_KEYS}
-
-
 def _check_scan(out, docs, blob, ref):
     assert out["doc_lines"].tolist() == [n for n, _, _ in ref]
     assert out["hist"].tolist() == [h for _, h, _ in ref]
@@ -536,7 +516,7 @@ def test_log_scan(eng, log_cases, fused):
                 walks.append(run_poisons(eng, lambda e: _scan_one_call(e, blob, off, 0)))
                 n_fallback += 1
             if fused == 0:  # the two-call protocol has no fused form
-                walks.append(run_poisons(eng, lambda e: _scan_two_calls(e, blob, off)))
+                walks.append(run_poisons(eng, lambda e: scan_two_calls(e, blob, off)))
             for w in walks[1:]:
                 _check_scan(w, docs, blob, ref)
                 for k in LOG_KEYS:

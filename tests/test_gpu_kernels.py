@@ -144,8 +144,45 @@ def _check_docs(eng, docs):
             assert scan.examples(d, c) == ex[c], (d, c)
 
 
-@pytest.mark.parametrize("knobs", [dict(KRCA_LOG_FUSED=0), dict(KRCA_LOG_FUSED=1), dict(KRCA_LOG_FUSED=2),
-                                   dict(KRCA_LOG_FUSED=0, KRCA_LOG_IMPL=1), dict(KRCA_LOG_FUSED=0, KRCA_LOG_IMPL=2)])
+LOG_KEYS = ("line_start", "line_end", "line_mask", "doc_lines", "doc_line0", "hist", "examples")
+
+
+def scan_one_call(e, blob, off):
+    """NativeEngine.log_scan_device with the dense example table (host copies): krca_log_scan, and
+    krca_log_match over the index it left when the engine's line arrays were too small."""
+    r = e.log_scan_device(e.upload_blob(blob), e._dev(np.asarray(off, np.int64)), dense_examples=True)
+    return {k: r[k].cpu().numpy() for k in LOG_KEYS}
+
+
+def scan_two_calls(e, blob, off):
+    """krca_log_index, then krca_log_match into line arrays of exactly the line count."""
+    t = e.torch
+    text, offd = e.upload_blob(blob), e._dev(np.asarray(off, np.int64))
+    nbytes, D = len(blob), len(off) - 1
+    ws = e._workspace("logidx", 8 * e.lib.krca_log_index_size(nbytes))
+    nl = t.empty(1, dtype=t.int64, device=e.device)
+    native._check(e.lib.krca_log_index(e.ptr(text), nbytes, e.ptr(offd), D, e.ptr(ws), e.ptr(nl), e._stream()),
+                  "krca_log_index")
+    L = int(nl.item())
+    new = lambda dt, *shape: t.empty(shape, dtype=dt, device=e.device)  # noqa: E731
+    r = dict(line_start=new(t.int64, L), line_end=new(t.int64, L), line_mask=new(t.int32, L), doc_lines=new(t.int32, D),
+             doc_line0=new(t.int64, D), hist=new(t.int32, D, native.NCAT), examples=new(t.int32, D, native.NCAT, 3))
+    native._check(e.lib.krca_log_match(e.ptr(text), nbytes, e.ptr(offd), D, e.ptr(ws), L, e.ptr(r["line_start"]),
+                                       e.ptr(r["line_end"]), e.ptr(r["line_mask"]), e.ptr(r["doc_lines"]),
+                                       e.ptr(r["hist"]), e.ptr(r["examples"]), e.ptr(r["doc_line0"]), e._stream()),
+                  "krca_log_match")
+    return {k: r[k].cpu().numpy().copy() for k in LOG_KEYS}
+
+
+def _check_one_call_equals_two_calls(eng, docs):
+    """Every output array of the one-call protocol byte-equal to the two-call protocol's."""
+    blob, off = pack_documents(docs)
+    one, two = scan_one_call(eng, blob, off), scan_two_calls(eng, blob, off)
+    for k in LOG_KEYS:
+        assert one[k].dtype == two[k].dtype and np.array_equal(one[k], two[k]), k
+
+
+@pytest.mark.parametrize("knobs", [dict(KRCA_LOG_FUSED=0), dict(KRCA_LOG_FUSED=1), dict(KRCA_LOG_FUSED=2)])
 def test_log_scan_no_match_across_container_end(eng, knobs):
     """A container without a trailing separator ends its last line: the next container's first
     bytes must not complete a pattern ("Erro" | "r", "StatusCode=50" | "0", "OOMKille" | "d"),
@@ -159,8 +196,7 @@ def test_log_scan_no_match_across_container_end(eng, knobs):
         _check_docs(eng, docs)
 
 
-@pytest.mark.parametrize("knobs", [dict(KRCA_LOG_FUSED=0), dict(KRCA_LOG_FUSED=1), dict(KRCA_LOG_FUSED=2),
-                                   dict(KRCA_LOG_FUSED=0, KRCA_LOG_IMPL=1), dict(KRCA_LOG_FUSED=0, KRCA_LOG_IMPL=2)])
+@pytest.mark.parametrize("knobs", [dict(KRCA_LOG_FUSED=0), dict(KRCA_LOG_FUSED=1), dict(KRCA_LOG_FUSED=2)])
 def test_log_scan_fragment_fuzz(eng, knobs):
     """Every literal alternative of the 13 patterns cut at a random point, its halves scattered
     over lines and containers with separators, multi-byte characters and fillers of random length
@@ -242,8 +278,10 @@ def test_log_scan_boundaries(eng):
 def test_log_scan_container_starts_at_tile_boundaries(eng):
     """Container starts placed exactly at 64 KiB tile boundaries (k*65536) and one byte before
     (k*65536-1), with \r / \n / CRLF pairs split across the container edge and empty containers
-    there: log_count / log_lines read the container starts of a tile (and the byte at tile0-1)
-    from a per-tile LDS bitmap."""
+    there: log_index_lines (the one call) and log_count / log_lines (reached only through
+    krca_log_index / krca_log_match) read the container starts of a tile (and the byte at tile0-1)
+    from a per-tile LDS bitmap.  The corpus goes through the one call and through the two-call
+    protocol; every output array is byte-equal."""
     TILE = 65536
     tails = ["\r", "x\r", "Error\n", "", "timeout"]
     heads = ["\nKilled", "\n", "\r\npanic:", "ERROR", "", "\x85z"]
@@ -264,28 +302,20 @@ def test_log_scan_container_starts_at_tile_boundaries(eng):
         pos += len(docs[-1].encode())
         k += 1
     _check_docs(eng, docs)
+    _check_one_call_equals_two_calls(eng, docs)
 
 
-def test_log_scan_impls_identical(eng, monkeypatch):
-    """The line-index + DFA-lane path (default) and the chunk-lane path (KRCA_LOG_IMPL=1) give the
-    same line offsets, masks, histograms and examples, long lines (> 1 KiB, a wave each) included."""
+def test_log_scan_long_lines_one_call_and_two_calls_identical(eng):
+    """krca_log_scan and the two-call protocol (krca_log_index, then krca_log_match: log_lines fills
+    the line arrays) give the same line offsets, masks, histograms and examples, long lines
+    (> 1 KiB, a wave each) and separators at container edges included; and the oracle's."""
     rng = np.random.default_rng(11)
     docs = synth.make_log_corpus(3000, lines_per_doc=4, seed=5, hazard_rate=0.02)
     docs += ["x" * 5000 + " Killed " + "y" * 3000 + "\n" + "z" * 1025 + "timeout", "é" * 2000 + "panic:",
              "a\r", "\nb", "ſ" * 700 + "Error" + "\u2028" + "k" * 1100, ""]
     docs += ["".join(rng.choice(["Error ", "\r\n", "é", "\x85", "OOMKilled", "w" * 300]) for _ in range(40))
              for _ in range(50)]
-    blob, off = pack_documents(docs)
-    tb, toff = eng.upload_blob(blob), torch.from_numpy(off).cuda()
-    out = {}
-    for impl in ("0", "1", "2"):
-        with native.tune(eng.lib, KRCA_LOG_IMPL=int(impl)):
-            r = eng.log_scan_device(tb, toff)
-            out[impl] = {k: v.cpu().numpy() for k, v in r.items() if hasattr(v, "cpu")}
-    for other in ("1", "2"):
-        assert out["0"].keys() == out[other].keys()
-        for k in out["0"]:
-            assert np.array_equal(out["0"][k], out[other][k]), (other, k)
+    _check_one_call_equals_two_calls(eng, docs)
     _check_docs(eng, docs)
 
 
@@ -338,15 +368,17 @@ def test_log_scan_one_call_and_fallback_identical(eng):
     tb, toff = eng.upload_blob(blob), torch.from_numpy(off).cuda()
     fresh = native.NativeEngine()
     out = []
-    for e, impl in ((fresh, 0), (fresh, 0), (eng, 1)):  # fallback (cap 1024), one call, two calls
-        with native.tune(e.lib, KRCA_LOG_IMPL=impl):
-            r = e.log_scan_device(tb, toff)
-            out.append({k: v.cpu().numpy() for k, v in r.items() if hasattr(v, "cpu")})
+    for _ in range(2):  # fallback (cap 1024), then one call
+        r = fresh.log_scan_device(tb, toff)
+        out.append({k: v.cpu().numpy() for k, v in r.items() if hasattr(v, "cpu")})
     assert fresh._log_cap >= out[0]["line_start"].shape[0]
-    for o in out[1:]:
-        for k in out[0]:
-            assert np.array_equal(out[0][k], o[k]), k
+    for k in out[0]:
+        assert np.array_equal(out[0][k], out[1][k]), k
+    two = scan_two_calls(eng, blob, off)  # krca_log_index, then krca_log_match
+    for k in LOG_KEYS[:-1]:  # (the dense example table is compared below)
+        assert out[0][k].dtype == two[k].dtype and np.array_equal(out[0][k], two[k]), k
     # the dense example table (A/B form) equals the example bits of the masks, in both protocols
+    assert np.array_equal(two["examples"], native.example_ids(two["line_mask"], two["doc_line0"], two["doc_lines"]))
     for e in (fresh, eng):
         r = e.log_scan_device(tb, toff, dense_examples=True)
         bits = native.example_ids(r["line_mask"].cpu().numpy(), r["doc_line0"].cpu().numpy(),

@@ -1,5 +1,5 @@
 #!/bin/bash
-# PMC passes on the log scan kernels (log_count / log_match / log_hist): one counter group per run,
+# PMC passes on the log scan kernels (log_index_lines / log_dfa / log_hist): one counter group per run,
 # no trace domains, each pass under its own kill timeout.  bash tools/gpu_pmc_logs.sh TAG
 set -u
 TAG=${1:-pmclogs}
