@@ -472,6 +472,47 @@ int krca_stream_score(const float* x_new, int64_t P, int32_t M, int32_t delta, i
                       float z_thr, void* state, float* z_last, float* score, int32_t* n_exceed, uint8_t* flags,
                       void* stream);
 
+/* ---- streaming anomaly timeline: krca_rolling_timeline carried forward over a stream, the episodes
+ * of every series kept between calls.  exceed(t), z = (float)(fabs(A) / sqrt(B)), the episode fields
+ * (onset, last, cnt, peak), gap, min_count and "sustained" are krca_rolling_timeline's.  New: the
+ * state lives between calls, and an episode stops being reported H steps after its last exceedance
+ * (the H that bounds n_exceed).  Per series, the state is the open episode (c_*) and the kept one
+ * (k_*); with `now` the global step being processed:
+ *   hit(t, z):   an open episode with t - c_last <= gap is extended (c_last = t, ++c_cnt, c_peak =
+ *                max(c_peak, z)); otherwise close(t), then a new episode opens at t.
+ *   close(now):  the open episode replaces the kept one when it is sustained and either the kept one
+ *                is absent or expired (now - k_last >= H), or c_peak >= k_peak.
+ *   view at the end of a call (now = t0 + delta - 1; it does not modify the state, the open episode
+ *                stays open for the next call): the kept episode is valid when it exists and
+ *                now - k_last < H; the open one is valid when it is sustained and now - c_last < H.
+ *                The series reports the open one when it is valid and the kept one is invalid or
+ *                c_peak >= k_peak; otherwise the kept one if valid; otherwise none.
+ * Per pod, the M views are combined exactly as krca_rolling_timeline combines kept episodes (anchor,
+ * members, the six outputs); onsets are global step indices.  Consequences: (1) while H exceeds the
+ * number of steps so far nothing expires, and after every call the six outputs equal
+ * krca_rolling_timeline over the whole series so far, bit for bit; (2) expiry is a function of
+ * (last, now) only, so the outputs at step `now` do not depend on how the steps were split into calls.
+ * state: krca_stream_score's rolling state (same layout, same size function); after each call its
+ * defined bytes and z_last / score / n_exceed / flags are what krca_stream_score leaves for the same
+ * input.  ep_state: krca_stream_episode_state_size bytes of plain data (no pointers; a copy to the
+ * host and back checkpoints it), 4-byte aligned: 4-byte planes [8][S] over the series S = P*M --
+ * c_on, c_last, c_cnt (int32), c_peak (float32), k_on, k_last, k_cnt (int32), k_peak (float32).
+ * Rules for the caller: a stream uses this call from t0 == 0 on, with the same W, H, gap and
+ * min_count every time; mixing it with krca_stream_score on the same state loses episodes (that call
+ * advances the sums and sees no exceedance).  t0 + delta <= INT32_MAX (onsets are int32), gap >= 0,
+ * min_count >= 1; P == 0 returns KRCA_OK.
+ * Buffers: state as for krca_stream_score.  ep_state needs no initialisation before the t0 == 0 call:
+ * that call ignores what it holds and every series stores its state at the end; a later call stores
+ * only the series whose episodes changed.  The four scoring outputs and onset / last / count / peak /
+ * lead / n_metrics [P] are fully written by every call (a pod that reports no episode: onset = last
+ * = -1, count = 0, peak = 0, lead = -1, n_metrics = 0). */
+int64_t krca_stream_episode_state_size(int64_t P, int32_t M);
+int krca_stream_timeline(const float* x_new, int64_t P, int32_t M, int32_t delta, int64_t t0, int32_t W, int32_t H,
+                         float z_thr, int32_t gap, int32_t min_count, void* state, void* ep_state,
+                         float* z_last, float* score, int32_t* n_exceed, uint8_t* flags, /* as krca_stream_score */
+                         int32_t* onset /*[P]*/, int32_t* last /*[P]*/, int32_t* count /*[P]*/, float* peak /*[P]*/,
+                         int8_t* lead /*[P]*/, uint8_t* n_metrics /*[P]*/, void* stream);
+
 /* ---- f3: betweenness centrality for the SPOF check (TopologyAgent._analyze_single_points_of_failure,
  * ref:agents/topology_agent.py:322-356, networkx 3.4.2 betweenness_centrality): Brandes over the
  * OUT-edge CSR (row u = successors of u), `batch` sources in flight (one workgroup each),

@@ -5,6 +5,7 @@
 //  krca_rolling_score  — rolling-window z-scores over a time-major [T][P][M] float32 tensor.
 //  krca_rolling_timeline — the same pass, also keeping WHEN each series exceeded: episodes of
 //                        exceedances in the exceed branch, combined per pod in the epilogue.
+//  krca_stream_score / krca_stream_timeline — the two carried forward over a stream, the state in HBM.
 //
 // Design (MI355X): HBM-streaming, one lane per series s = p*M + m.  At every time step a wave
 // reads 64 consecutive floats (256 B, fully coalesced) and the trailing window of W samples
@@ -140,17 +141,81 @@ struct Episodes {
   }
 };
 
-// Pod combine of the kept episodes, over the pod's M wave-aligned lanes (every lane of the wave
-// takes part in the shuffles; a lane past S contributes "no episode").  Anchor = the kept episode
-// of the largest peak (ties: lowest m); members = the kept episodes within `gap` of overlapping the
-// anchor's [onset, last].
-__device__ __forceinline__ void timeline_epilogue(Episodes& ep, int64_t s, bool active, int M,
-                                                  const TimelineOut& o) {
-  ep.close();
-  const bool has = active && ep.k_cnt > 0;
+// The streaming form (krca_stream_timeline; semantics in include/krca.h): the same two episodes,
+// loaded from and stored to the episode state [8][S] (planes c_on, c_last, c_cnt, c_peak, k_on,
+// k_last, k_cnt, k_peak: a wave's accesses are 256 consecutive bytes per plane), plus the horizon H
+// after which an episode stops being reported.  A separate type: the batch kernels instantiate
+// Episodes alone and carry none of this (rolling_score_pipe sits 5 VGPRs under its occupancy limit).
+struct StreamEpisodes : Episodes {
+  struct Args {
+    int gap, min_count, H;
+    int32_t* state;
+    TimelineOut out;
+  };
+  int H;
+  bool c_dirty, k_dirty;  // the open / the kept episode changed in this call: only then it is stored
+  __device__ __forceinline__ explicit StreamEpisodes(const Args& a)
+      : Episodes(Episodes::Args{a.gap, a.min_count, a.out}), H(a.H), c_dirty(false), k_dirty(false) {}
+  __device__ __forceinline__ void load(const int32_t* p, int64_t S, int64_t sl) {
+    c_on = p[sl];
+    c_last = p[S + sl];
+    c_cnt = p[2 * S + sl];
+    c_peak = __builtin_bit_cast(float, p[3 * S + sl]);
+    k_on = p[4 * S + sl];
+    k_last = p[5 * S + sl];
+    k_cnt = p[6 * S + sl];
+    k_peak = __builtin_bit_cast(float, p[7 * S + sl]);
+  }
+  __device__ __forceinline__ void store(int32_t* p, int64_t S, int64_t sl) const {
+    if (c_dirty) {
+      p[sl] = c_on;
+      p[S + sl] = c_last;
+      p[2 * S + sl] = c_cnt;
+      p[3 * S + sl] = __builtin_bit_cast(int32_t, c_peak);
+    }
+    if (k_dirty) {
+      p[4 * S + sl] = k_on;
+      p[5 * S + sl] = k_last;
+      p[6 * S + sl] = k_cnt;
+      p[7 * S + sl] = __builtin_bit_cast(int32_t, k_peak);
+    }
+  }
+  // the open episode ended at step `now`: it replaces the kept one if it is sustained and the kept
+  // one is absent, expired or no stronger
+  __device__ __forceinline__ void close(int now) {
+    if (c_cnt >= min_count && (k_cnt == 0 || now - k_last >= H || c_peak >= k_peak)) {
+      k_on = c_on;
+      k_last = c_last;
+      k_cnt = c_cnt;
+      k_peak = c_peak;
+      k_dirty = true;
+    }
+  }
+  __device__ __forceinline__ void hit(int t, double A, double B) {
+    const float z = (float)(fabs(A) / sqrt(B));
+    c_dirty = true;
+    if (c_cnt > 0 && t - c_last <= gap) {
+      c_last = t;
+      ++c_cnt;
+      c_peak = fmaxf(c_peak, z);
+    } else {
+      close(t);
+      c_on = c_last = t;
+      c_cnt = 1;
+      c_peak = z;
+    }
+  }
+};
+
+// Pod combine of one episode per series (`has`: the lane has one), over the pod's M wave-aligned
+// lanes (every lane of the wave takes part in the shuffles; a lane past S contributes "no
+// episode").  Anchor = the episode of the largest peak (ties: lowest m); members = the episodes
+// within `gap` of overlapping the anchor's [onset, last].
+__device__ __forceinline__ void timeline_combine(bool has, int e_on, int e_last, int e_cnt, float e_peak, int gap,
+                                                 int64_t s, bool active, int M, const TimelineOut& o) {
   const int lane = threadIdx.x & 63;
   const int m = lane & (M - 1);  // == s & (M - 1): workgroups start at a multiple of 256 series
-  float ap = has ? ep.k_peak : -1.f;
+  float ap = has ? e_peak : -1.f;
   int am = m;
   for (int off = 1; off < M; off <<= 1) {
     const float op = __shfl_xor(ap, off, 64);
@@ -161,11 +226,11 @@ __device__ __forceinline__ void timeline_epilogue(Episodes& ep, int64_t s, bool 
     }
   }
   const int src = (lane & ~(M - 1)) + am;
-  const int64_t a_on = __shfl(ep.k_on, src, 64), a_last = __shfl(ep.k_last, src, 64);
-  const bool mem = has && (int64_t)ep.k_on <= a_last + ep.gap && a_on <= (int64_t)ep.k_last + ep.gap;
-  long long first = mem ? (((long long)ep.k_on << 8) | m) : INT64_MAX;  // min: earliest onset, then lowest m
-  int lastv = mem ? ep.k_last : -1;
-  int cnt = mem ? ep.k_cnt : 0;
+  const int64_t a_on = __shfl(e_on, src, 64), a_last = __shfl(e_last, src, 64);
+  const bool mem = has && (int64_t)e_on <= a_last + gap && a_on <= (int64_t)e_last + gap;
+  long long first = mem ? (((long long)e_on << 8) | m) : INT64_MAX;  // min: earliest onset, then lowest m
+  int lastv = mem ? e_last : -1;
+  int cnt = mem ? e_cnt : 0;
   int nm = mem ? 1 : 0;
   for (int off = 1; off < M; off <<= 1) {
     const long long of = __shfl_xor(first, off, 64);
@@ -183,6 +248,26 @@ __device__ __forceinline__ void timeline_epilogue(Episodes& ep, int64_t s, bool 
   o.peak[p] = nm ? ap : 0.f;
   o.lead[p] = nm ? (int8_t)(first & 0xff) : (int8_t)-1;
   o.n_metrics[p] = (uint8_t)nm;
+}
+
+// krca_rolling_timeline: the series is over, so its open episode closes; the kept ones combine
+__device__ __forceinline__ void timeline_epilogue(Episodes& ep, int64_t s, bool active, int M,
+                                                  const TimelineOut& o) {
+  ep.close();
+  timeline_combine(active && ep.k_cnt > 0, ep.k_on, ep.k_last, ep.k_cnt, ep.k_peak, ep.gap, s, active, M, o);
+}
+
+// krca_stream_timeline: the view of the series at step `now` (the call's last step), formed on
+// copies -- the open episode stays open for the next call.  An episode is reported while
+// now - last < H; the open one must be sustained, and wins over a valid kept one on c_peak >= k_peak
+// (what close() would decide).
+__device__ __forceinline__ void stream_timeline_epilogue(const StreamEpisodes& ep, int now, int64_t s, bool active,
+                                                         int M, const TimelineOut& o) {
+  const bool k_ok = ep.k_cnt > 0 && now - ep.k_last < ep.H;
+  const bool c_ok = ep.c_cnt >= ep.min_count && now - ep.c_last < ep.H;
+  const bool use_c = c_ok && (!k_ok || ep.c_peak >= ep.k_peak);
+  timeline_combine(active && (use_c || k_ok), use_c ? ep.c_on : ep.k_on, use_c ? ep.c_last : ep.k_last,
+                   use_c ? ep.c_cnt : ep.k_cnt, use_c ? ep.c_peak : ep.k_peak, ep.gap, s, active, M, o);
 }
 
 // Pod epilogue shared by both kernels: z_last per series, pod max|z|, exceedance sum, flags.
@@ -436,20 +521,32 @@ struct StreamState {
   uint32_t* bits;
 };
 
+//
+// Ep = StreamEpisodes: krca_stream_timeline's form.  The lane's 8 words of episode state are loaded
+// with the sums (the latency overlaps the first sample loads), updated in the exceed branch and
+// stored only by the lanes whose episodes changed (the t0 == 0 call stores every lane's initial
+// state); the pod combine of the views runs behind the scorer's epilogue.  Per series and window it
+// adds 32 B of state read, and 18 B of outputs per pod.
+template <class Ep = NoEpisodes>
 __global__ __launch_bounds__(256) void stream_score(const float* __restrict__ xn, int64_t S, int delta, int64_t t0,
                                                     int W, int H, int M, double thr2, StreamState stt,
                                                     float* __restrict__ z_last, float* __restrict__ score,
-                                                    int32_t* __restrict__ n_exceed, uint8_t* __restrict__ flags) {
+                                                    int32_t* __restrict__ n_exceed, uint8_t* __restrict__ flags,
+                                                    typename Ep::Args targs) {
   const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const bool active = s < S;
   const int64_t sl = active ? s : 0;
   const double Wd = (double)W, epsB = kVarEps * Wd * Wd;
   StepState st{0.0, 0.0, 0, 0.0, 0.0};
+  Ep ep(targs);
   int cnt = 0;
   if (t0 > 0) {
     st.s1 = stt.s1[sl];
     st.s2 = stt.s2[sl];
     cnt = stt.cnt[sl];
+    if constexpr (Ep::kTrack) ep.load(targs.state, S, sl);
+  } else if constexpr (Ep::kTrack) {
+    ep.c_dirty = ep.k_dirty = true;  // the stream starts: whatever the state held is replaced
   }
   for (int j = 0; j < delta; ++j) {
     const int64_t t = t0 + j;
@@ -462,7 +559,7 @@ __global__ __launch_bounds__(256) void stream_score(const float* __restrict__ xn
     } else {
       const float o = *rp;
       st.cnt = 0;
-      step(st, v, o, Wd, epsB, thr2, j == delta - 1);
+      step(st, v, o, Wd, epsB, thr2, j == delta - 1, ep, (int)t);
       const int64_t e = t - W;  // index among the evaluated steps
       uint32_t* wp = stt.bits + ((e % H) >> 5) * S + sl;
       const uint32_t bit = 1u << ((e % H) & 31);
@@ -476,10 +573,12 @@ __global__ __launch_bounds__(256) void stream_score(const float* __restrict__ xn
     stt.s1[sl] = st.s1;
     stt.s2[sl] = st.s2;
     stt.cnt[sl] = cnt;
+    if constexpr (Ep::kTrack) ep.store(targs.state, S, sl);
   }
   st.cnt = cnt;
   if (t0 + delta - 1 < W) st.bl = 0.0;  // no evaluated step yet: z = 0
   pod_epilogue(st, epsB, s, active, M, delta, xn + sl, S, z_last, score, n_exceed, flags);
+  if constexpr (Ep::kTrack) stream_timeline_epilogue(ep, (int)(t0 + delta - 1), s, active, M, targs.out);
 }
 
 // rows per pipelined chunk: a divisor of W that keeps 10 .. 20 rows in flight per wave
@@ -570,13 +669,32 @@ int64_t krca_stream_state_size(int64_t P, int32_t M, int32_t W, int32_t H) {
   return S * (8 + 8 + 4) + (int64_t)W * S * 4 + krca::ceil_div(H, 32) * S * 4 + 64;
 }
 
-int krca_stream_score(const float* x_new, int64_t P, int32_t M, int32_t delta, int64_t t0, int32_t W, int32_t H,
-                      float z_thr, void* state, float* z_last, float* score, int32_t* n_exceed, uint8_t* flags,
-                      void* stream) {
-  KRCA_CHECK_ARG(P >= 0 && delta >= 1 && t0 >= 0 && W >= 1 && H >= 1, "krca_stream_score: bad sizes");
-  KRCA_CHECK_ARG(M >= 1 && M <= 64 && (M & (M - 1)) == 0, "krca_stream_score: M=%d must be a power of two <= 64", M);
+// episode state of krca_stream_timeline: int32 / float32 planes [8][S]
+int64_t krca_stream_episode_state_size(int64_t P, int32_t M) { return P * (int64_t)M * 8 * 4; }
+
+}  // extern "C"
+
+namespace {
+// krca_stream_score (Ep = NoEpisodes) and krca_stream_timeline (StreamEpisodes)
+template <class Ep>
+int launch_stream(const char* fn, const float* x_new, int64_t P, int32_t M, int32_t delta, int64_t t0, int32_t W,
+                  int32_t H, float z_thr, void* state, float* z_last, float* score, int32_t* n_exceed, uint8_t* flags,
+                  const typename Ep::Args& ea, void* stream) {
+  KRCA_CHECK_ARG(P >= 0 && delta >= 1 && t0 >= 0 && W >= 1 && H >= 1, "%s: bad sizes", fn);
+  KRCA_CHECK_ARG(M >= 1 && M <= 64 && (M & (M - 1)) == 0, "%s: M=%d must be a power of two <= 64", fn, M);
+  bool ptrs = x_new && state && z_last && score && n_exceed && flags;
+  if constexpr (Ep::kTrack) {
+    KRCA_CHECK_ARG(ea.gap >= 0 && ea.min_count >= 1, "%s: gap=%d must be >= 0, min_count=%d >= 1", fn, ea.gap,
+                   ea.min_count);
+    KRCA_CHECK_ARG(t0 + delta <= (int64_t)INT32_MAX, "%s: t0 + delta = %lld is past INT32_MAX (onsets are int32)", fn,
+                   (long long)(t0 + delta));
+    const TimelineOut& o = ea.out;
+    ptrs = ptrs && ea.state && o.onset && o.last && o.count && o.peak && o.lead && o.n_metrics;
+  }
   if (P == 0) return KRCA_OK;
-  KRCA_CHECK_ARG(x_new && state && z_last && score && n_exceed && flags, "krca_stream_score: null pointer");
+  KRCA_CHECK_ARG(ptrs, "%s: null pointer", fn);
+  if constexpr (Ep::kTrack)
+    KRCA_CHECK_ARG(((uintptr_t)ea.state & 3) == 0, "%s: the episode state must be 4-byte aligned", fn);
   const int64_t S = P * (int64_t)M;
   char* b = reinterpret_cast<char*>(state);
   StreamState stt;
@@ -587,10 +705,30 @@ int krca_stream_score(const float* x_new, int64_t P, int32_t M, int32_t delta, i
   stt.bits = reinterpret_cast<uint32_t*>(stt.ring + (int64_t)W * S);
   hipStream_t st = krca::as_stream(stream);
   if (t0 == 0) KRCA_HIP(hipMemsetAsync(stt.bits, 0, krca::ceil_div(H, 32) * S * 4, st));
-  hipLaunchKernelGGL(stream_score, dim3((unsigned)krca::ceil_div(S, 256)), dim3(256), 0, st, x_new, S, delta, t0, W,
-                     H, M, (double)z_thr * (double)z_thr, stt, z_last, score, n_exceed, flags);
+  hipLaunchKernelGGL(stream_score<Ep>, dim3((unsigned)krca::ceil_div(S, 256)), dim3(256), 0, st, x_new, S, delta, t0, W,
+                     H, M, (double)z_thr * (double)z_thr, stt, z_last, score, n_exceed, flags, ea);
   KRCA_LAUNCH_CHECK();
   return KRCA_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int krca_stream_score(const float* x_new, int64_t P, int32_t M, int32_t delta, int64_t t0, int32_t W, int32_t H,
+                      float z_thr, void* state, float* z_last, float* score, int32_t* n_exceed, uint8_t* flags,
+                      void* stream) {
+  return launch_stream<NoEpisodes>("krca_stream_score", x_new, P, M, delta, t0, W, H, z_thr, state, z_last, score,
+                                   n_exceed, flags, NoEpisodes::Args{}, stream);
+}
+
+int krca_stream_timeline(const float* x_new, int64_t P, int32_t M, int32_t delta, int64_t t0, int32_t W, int32_t H,
+                         float z_thr, int32_t gap, int32_t min_count, void* state, void* ep_state, float* z_last,
+                         float* score, int32_t* n_exceed, uint8_t* flags, int32_t* onset, int32_t* last, int32_t* count,
+                         float* peak, int8_t* lead, uint8_t* n_metrics, void* stream) {
+  const StreamEpisodes::Args ea{gap, min_count, H, reinterpret_cast<int32_t*>(ep_state),
+                                TimelineOut{onset, last, count, peak, lead, n_metrics}};
+  return launch_stream<StreamEpisodes>("krca_stream_timeline", x_new, P, M, delta, t0, W, H, z_thr, state, z_last,
+                                       score, n_exceed, flags, ea, stream);
 }
 
 int krca_usage_flags(const float* usage, int64_t P, uint8_t* flags, void* stream) {

@@ -36,6 +36,9 @@ SIGNATURES = {
     "krca_stream_state_size": (c_i64, [c_i64, c_i32, c_i32, c_i32]),
     "krca_stream_score": (c_i32, [c_vp, c_i64, c_i32, c_i32, c_i64, c_i32, c_i32, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp,
                                   c_vp]),
+    "krca_stream_episode_state_size": (c_i64, [c_i64, c_i32]),
+    "krca_stream_timeline": (c_i32, [c_vp, c_i64, c_i32, c_i32, c_i64, c_i32, c_i32, c_f32, c_i32, c_i32, c_vp, c_vp,
+                                     c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "krca_log_dfa_unicode": (ctypes.c_char_p, []),
     "krca_log_dfa_digest": (ctypes.c_uint64, []),
     "krca_log_index_size": (c_i64, [c_i64]),

@@ -410,6 +410,40 @@ class DeviceShard:
                                           p(o["n_exceed"]), p(o["flags"]), e._stream()), "krca_stream_score")
         return o
 
+    def stream_timeline(self, x_new, t0, horizon, gap, min_count):
+        """stream_score plus the episodes carried across windows (krca_stream_timeline): the same
+        rolling state and score outputs, and per pod the timeline tensors (NativeEngine.TIMELINE_KEYS)
+        of the episodes still reported `horizon` steps after their last exceedance.  A stream uses
+        either this or stream_score from its first window on, with the same gap / min_count."""
+        e, p = self.eng, self.eng.ptr
+        d, P, M = x_new.shape
+        self.M = int(M)
+        if P != self.n:
+            raise ValueError(f"stream window has {P} pods, the shard owns {self.n}")
+        self._ensure_stream(int(M), horizon)
+        self._ensure_episodes(int(M))
+        o = self.score_out
+        self._chk(e.lib.krca_stream_timeline(p(x_new), P, M, int(d), int(t0), self.cfg.window, int(horizon),
+                                             float(self.cfg.z_threshold), int(gap), int(min_count),
+                                             p(self._stream_state), p(self._episode_state), p(o["z_last"]),
+                                             p(o["score"]), p(o["n_exceed"]), p(o["flags"]), p(o["onset"]),
+                                             p(o["last"]), p(o["count"]), p(o["peak"]), p(o["lead"]),
+                                             p(o["n_metrics"]), e._stream()), "krca_stream_timeline")
+        return o
+
+    def _ensure_episodes(self, M):
+        """The episode state (krca_stream_episode_state_size bytes) and the six timeline outputs,
+        allocated once; the outputs join score_out."""
+        torch, e = self.torch, self.eng
+        if getattr(self, "_episode_state", None) is not None:
+            return
+        P, dev = self.n, e.device
+        nbytes = e.lib.krca_stream_episode_state_size(P, M)
+        self._episode_state = torch.zeros(max(int(nbytes), 4), dtype=torch.uint8, device=dev)
+        dt = dict(onset=torch.int32, last=torch.int32, count=torch.int32, peak=torch.float32, lead=torch.int8,
+                  n_metrics=torch.uint8)
+        self.score_out.update({k: torch.empty(max(P, 1), dtype=dt[k], device=dev) for k in e.TIMELINE_KEYS})
+
     def _ensure_stream(self, M, horizon):
         """The rolling state (krca_stream_state_size bytes) and the score outputs, allocated once."""
         torch, e = self.torch, self.eng
@@ -430,7 +464,10 @@ class DeviceShard:
         ranks of the last solve (the next window's warm start)."""
         self.M = int(M)
         self._ensure_stream(self.M, horizon)
-        return dict(stream_state=self._stream_state.cpu().numpy(), r=self.r[:self.n].cpu().numpy())
+        st = dict(stream_state=self._stream_state.cpu().numpy(), r=self.r[:self.n].cpu().numpy())
+        if getattr(self, "_episode_state", None) is not None:  # a stream_timeline stream: its episodes too
+            st["episode_state"] = self._episode_state.cpu().numpy()
+        return st
 
     def load_state_dict(self, st, M, horizon):
         torch = self.torch
@@ -440,6 +477,13 @@ class DeviceShard:
         if ss.shape != tuple(self._stream_state.shape) or r.shape != (self.n,):
             raise ValueError(f"snapshot state {ss.shape} / ranks {r.shape} do not fit this shard "
                              f"({tuple(self._stream_state.shape)} / ({self.n},))")
+        if "episode_state" in st:
+            self._ensure_episodes(self.M)
+            es = np.asarray(st["episode_state"], np.uint8)
+            if es.shape != tuple(self._episode_state.shape):
+                raise ValueError(f"snapshot episode state {es.shape} does not fit this shard "
+                                 f"({tuple(self._episode_state.shape)})")
+            self._episode_state.copy_(torch.from_numpy(es))
         self._stream_state.copy_(torch.from_numpy(ss))
         self.r[:self.n].copy_(torch.from_numpy(r))
 

@@ -10,6 +10,9 @@ pull-CSR.
    (float64 window sums, the last W samples and the exceedance bits of the last H evaluated steps
    stay in HBM), so a window costs O(n_local*M*delta) instead of re-reading the history; its
    outputs equal krca_rolling_score over the whole series so far, bit for bit.  No communication.
+   With timeline=True the call is krca_stream_timeline: the same state and scores, plus the
+   anomaly timeline's episodes carried across windows (8 words per series) and, per pod, the six
+   timeline tensors of the episodes at most `horizon` steps old; first_movers() ranks them.
 2. The window's log text of the rank's containers goes through krca_log_scan
    (13-pattern histograms per container, the reference's LogsAgent semantics,
    ref:agents/logs_agent.py:147-151) and krca_template_hash / krca_template_hist (error-template
@@ -37,17 +40,25 @@ SNAPSHOT_VERSION = 1
 
 class StreamingRCA:
     def __init__(self, engine, row_ptr, col, outdeg, n_metrics, cfg=None, horizon=1440, tol=1e-9, max_iter=100,
-                 check_every=4, comm=None, shard=None, partition=None):
+                 check_every=4, comm=None, shard=None, partition=None, timeline=False, gap=3, min_count=3):
         """row_ptr / col / outdeg: the whole mesh's pull-CSR (host arrays); this rank keeps its rows.
         comm: krca.rca.Comm (world, rank) — default one rank.  shard: a prepared per-rank backend
         (tests); default DeviceShard on `engine`.  partition: a krca.rca.Partition, or "balanced"
-        (pods + in-edges balanced ranges); default uniform ranges of ceil(N / G) pods."""
+        (pods + in-edges balanced ranges); default uniform ranges of ceil(N / G) pods.
+        timeline: carry the anomaly timeline's episodes across windows (krca_stream_timeline, gap /
+        min_count as krca_rolling_timeline's; an episode is reported for `horizon` steps after its
+        last exceedance): every window's scores then hold the six timeline tensors too, and
+        first_movers() ranks them."""
         self.eng = engine
         self.cfg = cfg or Config()
         self.comm = comm or Comm()
         self.N = int(len(outdeg))
         self.M = int(n_metrics)
         self.H = int(horizon)
+        self.timeline, self.gap, self.min_count = bool(timeline), int(gap), int(min_count)
+        self._csr = (row_ptr, col) if self.timeline else None  # first_movers: the whole pull-CSR
+        self._csr_dev = None
+        self.last_timeline = None
         self.tol, self.max_iter, self.check_every = float(tol), int(max_iter), int(check_every)
         if partition == "balanced":
             partition = Partition.balanced(row_ptr, self.comm.world)
@@ -103,9 +114,26 @@ class StreamingRCA:
         d, P, M = x_new.shape
         if P != self.hi - self.lo or M != self.M:
             raise ValueError(f"stream window shape {tuple(x_new.shape)}: rank owns {self.hi - self.lo} pods x {self.M}")
-        o = self.shard.stream_score(x_new, self.t, self.H)
+        if self.timeline:
+            o = self.shard.stream_timeline(x_new, self.t, self.H, self.gap, self.min_count)
+            self.last_timeline = o
+        else:
+            o = self.shard.stream_score(x_new, self.t, self.H)
         self.t += int(d)
         return o
+
+    def first_movers(self, k=10, slack=0, explain=()):
+        """NativeEngine.first_movers on the last window's timeline over the whole pull-CSR (uploaded
+        once and kept).  One rank only: precedence sharded over ranks does not exist yet."""
+        if self.comm.world > 1:
+            raise ValueError("StreamingRCA.first_movers: onset precedence runs on one rank (world == 1)")
+        if not self.timeline:
+            raise ValueError("StreamingRCA.first_movers: the stream was built without timeline=True")
+        if self.last_timeline is None:
+            raise ValueError("StreamingRCA.first_movers: no window has been pushed yet")
+        if self._csr_dev is None:
+            self._csr_dev = self.eng._csr_dev(*self._csr)
+        return self.eng.first_movers(self.last_timeline, *self._csr_dev, slack=slack, k=k, explain=explain)
 
     # -- 2. logs ---------------------------------------------------------------------------------
     def push_logs(self, text, doc_off, templates=True, validate=True, _defer=False):
@@ -226,9 +254,12 @@ class StreamingRCA:
 
     # -- 4. snapshots ----------------------------------------------------------------------------
     def _meta(self):
-        return dict(version=SNAPSHOT_VERSION, shard=type(self.shard).__name__, N=self.N, M=self.M, H=self.H,
+        meta = dict(version=SNAPSHOT_VERSION, shard=type(self.shard).__name__, N=self.N, M=self.M, H=self.H,
                     lo=self.lo, hi=self.hi, n_max=self.n_max, world=self.comm.world, rank=self.comm.rank,
                     cfg=self.cfg.as_dict(), tol=self.tol)
+        if self.timeline:  # a stream without the timeline writes the keys it always wrote
+            meta.update(timeline=True, gap=self.gap, min_count=self.min_count)
+        return meta
 
     def snapshot(self, path):
         """Write this rank's stream state to `path` (.npz; each rank its own file, e.g. a path with
@@ -251,9 +282,14 @@ class StreamingRCA:
             arrays = {k: z[k] for k in z.files if k != "meta"}
         want = json.loads(json.dumps(self._meta(), sort_keys=True))
         diff = sorted(k for k in want if meta.get(k) != want[k])
+        if bool(meta.get("timeline", False)) != self.timeline and "timeline" not in diff:
+            diff.append("timeline")  # a timeline snapshot into a stream without one
         if diff:
             raise ValueError(f"snapshot {path} does not match this stream: {', '.join(diff)} differ")
+        if self.timeline and "episode_state" not in arrays:
+            raise ValueError(f"snapshot {path} holds no episode state")
         self.shard.load_state_dict(arrays, self.M, self.H)
+        self.last_timeline = None  # the next window writes it
         self.t, self.solved, self.last_iters = int(meta["t"]), bool(meta["solved"]), int(meta["last_iters"])
 
 
@@ -263,3 +299,11 @@ def window_bytes(P, M, delta):
     read + written; outputs 4*M + 9 B per pod."""
     S = P * M
     return S * (40 + 20 * delta) + P * (4 * M + 9)
+
+
+def timeline_window_bytes(P, M, delta):
+    """Algorithmic HBM bytes of one krca_stream_timeline call: window_bytes, plus the 8 words of
+    episode state read per series (32 B; they are written back only by the series that exceeded in
+    the window, which the model leaves out), plus the six timeline outputs per pod (onset, last,
+    count, peak 4 B each, lead and n_metrics 1 B each: 18 B)."""
+    return window_bytes(P, M, delta) + P * M * 32 + P * 18

@@ -17,6 +17,9 @@ produces) and on seeded onsets for 1 %, 10 % and 30 % of the pods.
 synth.make_metrics_onsets, for the default, spread and held-out chain root sets, hop delay 0 / 5 / 20
 steps and root onsets 3 and 30 steps before the end: NativeEngine.first_movers beside the score alone
 and the shipped RcaStep ranking (key "explained").  Recorded, not gated.  Needs an MI355X.
+
+--recall --stream-horizon H adds the first movers of the streaming timeline (krca_stream_timeline,
+episodes reported for H steps after their last exceedance) as `first_movers_stream`.
 """
 import argparse
 import json
@@ -116,6 +119,7 @@ def recall(a):
     import torch
     from krca import native, synth
     from krca.rca import Comm, Config, DeviceShard, RcaStep, shard_graph
+    from krca.stream import StreamingRCA
     eng = native.NativeEngine(0)
     P, E, T = 10_000, 200_000, 1440
     rows = []
@@ -123,6 +127,8 @@ def recall(a):
         for t_back in (3, 30):
             for delay in (0, 5, 20):
                 hit = {"first_movers": [], "score": [], "explained": []}
+                if a.stream_horizon:  # the streaming timeline: episodes older than the horizon are not reported
+                    hit["first_movers_stream"] = []
                 for seed in range(a.seeds):
                     m = synth.make_graph(P, n_edges=E, seed=seed)
                     if model == "chain":
@@ -136,6 +142,12 @@ def recall(a):
                     tl = eng.rolling_timeline_device(x, 60, 3.0, 3, 3)
                     hit["first_movers"].append(rec(eng.first_movers(tl, m.row_ptr, m.col, slack=a.slack, k=10)["idx"]))
                     hit["score"].append(rec(eng.topk_device(tl["score"], 10)[0].cpu().numpy()))
+                    if a.stream_horizon:  # one call: the outputs do not depend on how the steps are split
+                        s = StreamingRCA(eng, m.row_ptr, m.col, m.outdeg, 8, Config(), horizon=a.stream_horizon,
+                                         timeline=True)
+                        s.push_metrics(x)
+                        hit["first_movers_stream"].append(rec(s.first_movers(k=10, slack=a.slack)["idx"]))
+                        del s
                     c = Config().replace(seed_floor=None)
                     step = RcaStep(DeviceShard(eng, x, *shard_graph(m.row_ptr, m.col, m.outdeg, 0, P), P, P, 1, c),
                                    Comm(), c, 0)
@@ -147,6 +159,7 @@ def recall(a):
                 rows.append(row)
                 print(json.dumps(row), flush=True)
     return {"device": torch.cuda.get_device_name(0), "library": native.library_info(),
+            **({"stream_horizon": a.stream_horizon} if a.stream_horizon else {}),
             "mesh": f"C2: {P} pods / {E} edges, 8 metrics x {T} steps, seeds 0..{a.seeds - 1}",
             "metric": "top-10 recall of the planted roots (10 per mesh)", "rows": rows}
 
@@ -162,6 +175,8 @@ def main():
     ap.add_argument("--slack", type=int, default=2)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--runs", type=int, default=20)
+    ap.add_argument("--stream-horizon", type=int, default=0,
+                    help="--recall: also rank the first movers of StreamingRCA(timeline=True, horizon=H)")
     ap.add_argument("--out")
     a = ap.parse_args()
     out = recall(a) if a.recall else cost(a)
