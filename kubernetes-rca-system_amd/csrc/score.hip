@@ -9,8 +9,9 @@
 //
 // Design (MI355X): HBM-streaming, one lane per series s = p*M + m.  At every time step a wave
 // reads 64 consecutive floats (256 B, fully coalesced) and the trailing window of W samples
-// lives in registers (a W-entry ring indexed by the compile-time position inside an unrolled
-// W-step block), so each input byte crosses HBM exactly once: 4*P*M*T bytes per call.  The
+// lives in registers (a ring indexed by the compile-time position inside an unrolled block: W
+// entries, or W + D with D rows of prefetch in the pipelined kernel, score_walk.h), so each input
+// byte crosses HBM exactly once: 4*P*M*T bytes per call.  The
 // window statistics are float64 sliding sums updated in a FIXED order, so the integer outputs
 // (n_exceed, flags) are bit-identical to the C restatement in oracle/krca_oracle.c; the
 // threshold test is |z| > thr  <=>  A^2 > thr^2*B (A = W*x - s1, B = W*s2 - s1^2), with no
@@ -18,12 +19,18 @@
 // Pod-level reductions (max |z|, sum of exceedances, flag OR) are wave shuffles inside the
 // aligned M-lane group of the pod.
 #include "krca_common.h"
+#include "score_walk.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr double kVarEps = 1e-12;
+// the step arithmetic and the pipelined kernel's per-series walk (host and device code)
+using krca_walk::kVarEps;
+using krca_walk::prefetch_rows;
+using krca_walk::score_walk;
+using krca_walk::step;
+using krca_walk::StepState;
 
 __global__ __launch_bounds__(256) void usage_flags_kernel(const float2* __restrict__ usage, int64_t P,
                                                           uint8_t* __restrict__ flags) {
@@ -35,34 +42,7 @@ __global__ __launch_bounds__(256) void usage_flags_kernel(const float2* __restri
   }
 }
 
-struct StepState {
-  double s1, s2;  // window sum and sum of squares (float64, fixed order)
-  int cnt;        // exceedances of this series
-  double al, bl;  // A and B (below) at t = T-1
-};
-
-// One time step of the rolling statistics; `old` is x[t-W].  With A = W*x_t - s1 and
-// B = W*s2 - s1^2 (= W^2 * var, ddof 0):  z = A / sqrt(B),  |z| > thr  <=>  A^2 > thr^2 * B,
-// var > 1e-12  <=>  B > 1e-12 * W^2 — 13 float64 operations per sample, no division or sqrt.
-// The fma()s are explicit (and mirrored in oracle/krca_oracle.c): one rounding each.
-__device__ __forceinline__ void step(StepState& st, float v, float old, double Wd, double epsB, double thr2,
-                                     bool last) {
-  const double vd = (double)v;
-  const double od = (double)old;
-  const double A = fma(Wd, vd, -st.s1);
-  const double B = fma(Wd, st.s2, -(st.s1 * st.s1));
-  st.cnt += (B > epsB) && (fma(A, A, -(thr2 * B)) > 0.0);
-  if (last) {
-    st.al = A;
-    st.bl = B;
-  }
-  st.s1 = (st.s1 + vd) - od;
-  st.s2 = fma(-od, od, fma(vd, vd, st.s2));
-}
-
-// The same step for the kernels that exist in a scoring and a timeline form.  `ep` sees the
-// exceedances only: NoEpisodes for krca_rolling_score (plain step(): the code of its kernels is what
-// it was without the parameter), Episodes for krca_rolling_timeline (step t of the series).
+// Episode policies of krca_walk::step().  NoEpisodes: the scorer, nothing tracked.
 struct NoEpisodes {
   static constexpr bool kTrack = false;
   struct Args {};
@@ -77,28 +57,6 @@ struct TimelineOut {
   int8_t* lead;
   uint8_t* n_metrics;
 };
-
-template <class Ep>
-__device__ __forceinline__ void step(StepState& st, float v, float old, double Wd, double epsB, double thr2,
-                                     bool last, Ep& ep, int t) {
-  if constexpr (!Ep::kTrack) {
-    step(st, v, old, Wd, epsB, thr2, last);
-  } else {
-    const double vd = (double)v;
-    const double od = (double)old;
-    const double A = fma(Wd, vd, -st.s1);
-    const double B = fma(Wd, st.s2, -(st.s1 * st.s1));
-    const bool exceed = (B > epsB) && (fma(A, A, -(thr2 * B)) > 0.0);
-    st.cnt += exceed;
-    if (exceed) ep.hit(t, A, B);  // rare and divergent; the only place episode state is touched
-    if (last) {
-      st.al = A;
-      st.bl = B;
-    }
-    st.s1 = (st.s1 + vd) - od;
-    st.s2 = fma(-od, od, fma(vd, vd, st.s2));
-  }
-}
 
 // Episode state of one series (krca_rolling_timeline; semantics in include/krca.h): the open
 // episode (c_*) and the kept one (k_*) = the sustained episode (cnt >= min_count) of the largest
@@ -145,7 +103,8 @@ struct Episodes {
 // loaded from and stored to the episode state [8][S] (planes c_on, c_last, c_cnt, c_peak, k_on,
 // k_last, k_cnt, k_peak: a wave's accesses are 256 consecutive bytes per plane), plus the horizon H
 // after which an episode stops being reported.  A separate type: the batch kernels instantiate
-// Episodes alone and carry none of this (rolling_score_pipe sits 5 VGPRs under its occupancy limit).
+// Episodes alone and carry none of this (rolling_score_pipe<60, 20> takes 124 VGPRs as the scorer, 4
+// under the 128 of four waves per SIMD, and 140 with Episodes: DESIGN.md §3.13, Registers).
 struct StreamEpisodes : Episodes {
   struct Args {
     int gap, min_count, H;
@@ -350,43 +309,47 @@ __device__ __forceinline__ float bload(__amdgpu_buffer_rsrc_t r, uint32_t voff, 
   return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, (int)voff, (int)soff, AUX));
 }
 
-// Software-pipelined form of rolling_score_ring over buffer loads (same arithmetic, same bits).  The
-// time axis is walked in C-row chunks (W % C == 0, so every ring slot index stays static); the loads of
-// chunk c+1 are issued before chunk c is computed, so each wave keeps C rows (C*256 B) in flight
-// through its whole compute phase instead of alternating load bursts and VALU bursts.  Only the
-// final block (the one holding t = T-1) tracks the last-step A/B, so the steady-state loop has
-// no per-sample select.  Buffer descriptors cover exactly the rows < T of a chunk: loads past the
-// end return 0 and touch no memory, which lets the prefetch run ahead unconditionally.
-template <int C>
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t chunk_rsrc(const float* x, int64_t S, uint32_t rowb, int t,
-                                                             int T) {
-  int n = T - t;
-  n = n < 0 ? 0 : (n > C ? C : n);
-  n = __builtin_amdgcn_readfirstlane(n);  // wave-uniform: keeps the descriptor in SGPRs (no v_med3 waterfall)
-  return __builtin_amdgcn_make_buffer_rsrc((void*)(x + (int64_t)(n ? t : 0) * S), 0, (int)(rowb * (uint32_t)n),
+// Software-pipelined form of rolling_score_ring over buffer loads (same arithmetic, same bits): the
+// walk of score_walk.h, a rotating ring of W + D sample registers whose loads leave one per step,
+// D rows ahead of their use, so each wave keeps about D rows (D*256 B) in flight through its whole
+// compute phase and no sample is copied between registers.  Buffer descriptors cover exactly the
+// rows < T of a group: loads past the end return 0 and touch no memory, which lets the prefetch run
+// ahead unconditionally.
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t span_rsrc(const float* x, int64_t S, uint32_t rowb, int t, int n,
+                                                            int T) {
+  int m = T - t;
+  m = m < 0 ? 0 : (m > n ? n : m);
+  m = __builtin_amdgcn_readfirstlane(m);  // wave-uniform: keeps the descriptor in SGPRs (no v_med3 waterfall)
+  return __builtin_amdgcn_make_buffer_rsrc((void*)(x + (int64_t)(m ? t : 0) * S), 0, (int)(rowb * (uint32_t)m),
                                            0x00020000);
 }
 
-// Row sources of the pipelined kernel.  SpanRows: one descriptor per chunk spanning its C rows
-// (needs 4*S*C < 2^31: up to ~3.3M pods x 8 metrics at C = 20).  BlockRows: one descriptor per
-// row covering only the workgroup's 256 series (base = x + t*S + s0), so any S < 2^32 works; it
-// costs a few scalar instructions per row, off the vector path.
+// Row sources of the pipelined kernel (the interface is score_walk()'s).  SpanRows: one descriptor
+// per group spanning its n <= D rows (needs 4*S*D < 2^31: up to ~3.3M pods x 8 metrics at D = 20),
+// rebuilt by scalar code.  BlockRows: one descriptor per row covering only the workgroup's 256
+// series (base = x + t*S + s0), so any S < 2^32 works; it costs a few scalar instructions per row,
+// off the vector path.
 struct SpanRows {
+  struct Group {
+    __amdgpu_buffer_rsrc_t rs;
+  };
   const float* x;
   int64_t S;
   uint32_t rowb, voff;
   int T;
   __device__ __forceinline__ SpanRows(const float* x_, int64_t S_, int T_, int64_t s, bool active)
       : x(x_), S(S_), rowb((uint32_t)(S_ * 4)), voff(active ? (uint32_t)s * 4u : 0u), T(T_) {}
-  template <int C, int AUX>
-  __device__ __forceinline__ void load(int t, float (&out)[C]) const {
-    const __amdgpu_buffer_rsrc_t rs = chunk_rsrc<C>(x, S, rowb, t, T);
-#pragma unroll
-    for (int j = 0; j < C; ++j) out[j] = bload<AUX>(rs, voff, rowb * j);
+  __device__ __forceinline__ Group group(int t, int n) const { return Group{span_rsrc(x, S, rowb, t, n, T)}; }
+  template <int AUX>
+  __device__ __forceinline__ float load(const Group& g, int j) const {
+    return bload<AUX>(g.rs, voff, rowb * (uint32_t)j);
   }
 };
 
 struct BlockRows {
+  struct Group {
+    int t;
+  };
   const float* xb;  // x + s0, s0 = the workgroup's first series
   int64_t S;
   uint32_t voff;
@@ -399,79 +362,31 @@ struct BlockRows {
     const int64_t n = S_ - s0;
     nrec = __builtin_amdgcn_readfirstlane((int)(4 * (n < (int64_t)blockDim.x ? n : (int64_t)blockDim.x)));
   }
-  template <int C, int AUX>
-  __device__ __forceinline__ void load(int t, float (&out)[C]) const {
-#pragma unroll
-    for (int j = 0; j < C; ++j) {
-      const int tt = t + j;
-      const bool in = tt < T;
-      const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-          (void*)(xb + (int64_t)(in ? tt : 0) * S), 0, in ? nrec : 0, 0x00020000);
-      out[j] = bload<AUX>(rs, voff, 0);
-    }
+  __device__ __forceinline__ Group group(int t, int) const { return Group{t}; }
+  template <int AUX>
+  __device__ __forceinline__ float load(const Group& g, int j) const {
+    const int tt = g.t + j;
+    const bool in = tt < T;
+    const __amdgpu_buffer_rsrc_t rs =
+        __builtin_amdgcn_make_buffer_rsrc((void*)(xb + (int64_t)(in ? tt : 0) * S), 0, in ? nrec : 0, 0x00020000);
+    return bload<AUX>(rs, voff, 0);
   }
 };
 
 // Ep = Episodes: krca_rolling_timeline's form of the same pass (the episode state in the exceed
 // branch, the pod combine of the kept episodes behind the scorer's epilogue).
-template <int W, int C, int AUX = 0, class Rows = SpanRows, class Ep = NoEpisodes>
+template <int W, int D, int AUX = 0, class Rows = SpanRows, class Ep = NoEpisodes>
 __global__ __launch_bounds__(256) void rolling_score_pipe(const float* __restrict__ x, int64_t S, int T, int M,
                                                           double thr2, float* __restrict__ z_last,
                                                           float* __restrict__ score, int32_t* __restrict__ n_exceed,
                                                           uint8_t* __restrict__ flags, typename Ep::Args targs) {
-  static_assert(W % C == 0, "chunk must divide the window");
-  constexpr int NC = W / C;
   const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const bool active = s < S;
   const Rows rows(x, S, T, s, active);
-  const double Wd = (double)W, epsB = kVarEps * Wd * Wd;
   StepState st{0.0, 0.0, 0, 0.0, 0.0};
   Ep ep(targs);
-  float ring[W];
-  float cur[C];
-  // prologue: rows [0, W) fill the window (requires T > W, checked by the launcher)
-#pragma unroll
-  for (int c = 0; c < NC; ++c) {
-    float tmp[C];
-    rows.template load<C, AUX>(c * C, tmp);
-#pragma unroll
-    for (int j = 0; j < C; ++j) ring[c * C + j] = tmp[j];
-  }
-  rows.template load<C, AUX>(W, cur);
-#pragma unroll
-  for (int j = 0; j < W; ++j) {
-    const double vd = (double)ring[j];
-    st.s1 = st.s1 + vd;
-    st.s2 = fma(vd, vd, st.s2);
-  }
-  int t0 = W;
-  for (; t0 + W < T; t0 += W) {  // full blocks that do not contain t = T-1
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      float nxt[C];
-      rows.template load<C, AUX>(t0 + (c + 1) * C, nxt);
-#pragma unroll
-      for (int j = 0; j < C; ++j) {
-        step(st, cur[j], ring[c * C + j], Wd, epsB, thr2, false, ep, t0 + c * C + j);
-        ring[c * C + j] = cur[j];
-      }
-#pragma unroll
-      for (int j = 0; j < C; ++j) cur[j] = nxt[j];
-    }
-  }
-  // final block: rows [t0, T), 1..W of them; cur already holds rows [t0, t0 + C)
-#pragma unroll
-  for (int c = 0; c < NC; ++c) {
-    if (c > 0) rows.template load<C, AUX>(t0 + c * C, cur);
-#pragma unroll
-    for (int j = 0; j < C; ++j) {
-      const int t = t0 + c * C + j;
-      if (t < T) {
-        step(st, cur[j], ring[c * C + j], Wd, epsB, thr2, t == T - 1, ep, t);
-        ring[c * C + j] = cur[j];
-      }
-    }
-  }
+  score_walk<W, D, AUX>(rows, T, thr2, st, ep);  // requires T > W, checked by the launcher
+  const double Wd = (double)W, epsB = kVarEps * Wd * Wd;
   pod_epilogue(st, epsB, s, active, M, T, x + (active ? s : 0), S, z_last, score, n_exceed, flags);
   if constexpr (Ep::kTrack) timeline_epilogue(ep, s, active, M, targs.out);
 }
@@ -581,8 +496,6 @@ __global__ __launch_bounds__(256) void stream_score(const float* __restrict__ xn
   if constexpr (Ep::kTrack) stream_timeline_epilogue(ep, (int)(t0 + delta - 1), s, active, M, targs.out);
 }
 
-// rows per pipelined chunk: a divisor of W that keeps 10 .. 20 rows in flight per wave
-constexpr int rows_per_chunk(int W) { return W == 60 ? 20 : (W == 30 ? 15 : (W == 20 ? 10 : W)); }
 bool pipe_window(int W) { return W == 60 || W == 30 || W == 20 || W == 15 || W == 10; }
 
 // the metric stream is read once: non-temporal loads (cache policy nt), 6.17 -> 6.61 TB/s at C4
@@ -612,12 +525,12 @@ void launch_reread(const ScoreCall& c, const typename Ep::Args& ea) {
 // wherever the scorer runs it (T <= W, or forced).
 template <int W, class Ep>
 void launch_window(int variant, const ScoreCall& c, const typename Ep::Args& ea) {
-  constexpr int C = rows_per_chunk(W);
+  constexpr int D = prefetch_rows(W);
   if (variant == KRCA_SCORE_PIPE)
-    hipLaunchKernelGGL((rolling_score_pipe<W, C, kNt, SpanRows, Ep>), c.grid, dim3(256), 0, c.st, c.x, c.S, c.T, c.M,
+    hipLaunchKernelGGL((rolling_score_pipe<W, D, kNt, SpanRows, Ep>), c.grid, dim3(256), 0, c.st, c.x, c.S, c.T, c.M,
                        c.thr2, c.z_last, c.score, c.n_exceed, c.flags, ea);
   else if (variant == KRCA_SCORE_PIPE_ROWS)
-    hipLaunchKernelGGL((rolling_score_pipe<W, C, kNt, BlockRows, Ep>), c.grid, dim3(256), 0, c.st, c.x, c.S, c.T, c.M,
+    hipLaunchKernelGGL((rolling_score_pipe<W, D, kNt, BlockRows, Ep>), c.grid, dim3(256), 0, c.st, c.x, c.S, c.T, c.M,
                        c.thr2, c.z_last, c.score, c.n_exceed, c.flags, ea);
   else if constexpr (Ep::kTrack)
     launch_reread<Ep>(c, ea);
@@ -747,7 +660,7 @@ int krca_rolling_score_variant(int64_t P, int32_t M, int32_t T, int32_t W) {
   if (!pipe_window(W)) return KRCA_SCORE_REREAD;
   if (T <= W || impl == KRCA_SCORE_RING) return KRCA_SCORE_RING;
   if (impl == KRCA_SCORE_PIPE_ROWS) return KRCA_SCORE_PIPE_ROWS;
-  return P * (int64_t)M * 4 * rows_per_chunk(W) < (int64_t(1) << 31) ? KRCA_SCORE_PIPE : KRCA_SCORE_PIPE_ROWS;
+  return P * (int64_t)M * 4 * prefetch_rows(W) < (int64_t(1) << 31) ? KRCA_SCORE_PIPE : KRCA_SCORE_PIPE_ROWS;
 }
 
 int krca_rolling_score(const float* x, int64_t P, int32_t M, int32_t T, int32_t W, float z_thr, float* z_last,
