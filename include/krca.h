@@ -202,6 +202,89 @@ int krca_log_scan(const uint8_t* text, int64_t nbytes, const int64_t* doc_off, i
                   int32_t* doc_lines /*[D]*/, int32_t* hist /*[D][13]*/, int32_t* examples /*[D][13][3], nullable*/,
                   int64_t* doc_line0 /*[D], nullable*/, int64_t* n_lines_host, void* stream);
 
+/* ---- a11/a12 with pattern tables compiled at run time -------------------------------------------
+ * The calls above match the 13 patterns compiled into the library.  These match any pattern set the
+ * host compiler (krca/logdfa.py compile_patterns) accepts: same text / doc_off contract, same lines,
+ * same line_mask layout (bits 0..ncat-1 the categories, bits 16..16+ncat-1 the example marks), with
+ * hist [D][ncat] and examples [D][ncat][3] strided by the tables' ncat.
+ *
+ * Pattern subset: every regex expands to a finite set of fixed-length alternatives of
+ * single-code-point atoms (literals, '.', \d \D \w \W \s \S, bracket classes; {n}, {m,n}, ? on one
+ * atom).  No unbounded quantifier: the wave-per-line kernel for lines over 1 KiB starts each of its
+ * 64 segments from the start state after a warm-up of `warm` code points (the longest alternative
+ * minus one), which is exact only when no match is longer than warm + 1 code points.
+ *
+ * Table image (host memory, little-endian, version 1):
+ *   offset  0  uint32 magic = KRCA_LOG_IMAGE_MAGIC, version = KRCA_LOG_IMAGE_VERSION,
+ *              ncat, nsym, nstate, nrange, warm, other   (eight uint32)
+ *          32  uint64 digest (patterns.pattern_digest of the (name, regex) pairs)
+ *          40  uint32 nbytes (the whole image), uint32 0
+ *          48  uint8  ascii_sym[128]        symbol of each ASCII code point, KRCA_LOG_SYM_SEP for a separator
+ *         176  uint32 ranges[nrange][3]     {lo, hi, symbol}: non-ASCII code points, every other one -> `other`
+ *              uint16 trans[nstate * nsym]  target state of (state, symbol); state 0 is the start state
+ *              uint16 out[nstate]           category mask reported on entering the state
+ *              zero padding to a multiple of 8 bytes
+ * Limits: 1 <= ncat <= 16, 1 <= nsym <= 63, 1 <= nstate <= 1024, nrange <= 1024, warm <= 63.
+ *
+ * krca_log_tables_check (host only, no GPU needed): validates an image -- magic, version, sizes, the
+ *   limits, every transition < nstate, every mask < 1 << ncat, ranges sorted, disjoint, lo <= hi, above
+ *   0x7F and below 0x110000, every symbol < nsym (or KRCA_LOG_SYM_SEP) and other < nsym -- and fills
+ *   *dims (nullable).  KRCA_EINVAL with krca_last_error() naming the field otherwise.
+ * krca_log_tables_dev_size (host only): bytes of the device form for these dimensions (0 when they
+ *   break a limit).  The device form is the walk kernels' LDS layout, copied as it is: 16-bit entries
+ *   (target state | 0x8000 when the target reports a category; category masks are read from out[]
+ *   on flagged entries only) in rows of 32 columns (nsym <= 31) or 64, the last column the identity
+ *   for bytes outside the line and UTF-8 continuation bytes; out[]; the byte -> symbol table; ranges.
+ *   16-bit entries hold every set inside the limits in one form (1024 states x 64 columns = 128 KiB
+ *   of the CU's 160 KiB; 32-bit entries carrying the masks stop at 640 states of 64 columns) and keep
+ *   the 13 shipped patterns at 25 KB where the compiled walk's 32-bit table takes 49 KB.
+ * krca_log_tables_upload: validates the image first (nothing is written when it fails), then writes the
+ *   device form to tables_dev [tables_dev_bytes >= krca_log_tables_dev_size] on `stream` and
+ *   synchronises it; *dims receives the dimensions the scan calls take.
+ * krca_log_scan_tables / krca_log_match_tables mirror krca_log_scan / krca_log_match (same workspace:
+ *   krca_log_index_size; krca_log_index is pattern-independent and serves both).  They re-check *dims
+ *   against the limits and tables_dev_bytes against the device form's size, ask the runtime how much
+ *   LDS a launch may take (opting in above the default), and fail with KRCA_EINVAL before any launch
+ *   when the table cannot be launched.  The kernels sanitise what they copy into LDS (targets clamped
+ *   to nstate - 1, symbols to the row width, masks to ncat bits), so a corrupted device form gives
+ *   wrong masks but never an index outside the LDS allocation.
+ *   KRCA_LOG_FUSED does not apply to these calls: they always run the two-pass path (line index, then
+ *   the walk).
+ * Buffers: as krca_log_scan / krca_log_match -- the workspace and every output need no initialisation;
+ *   line arrays [0, n_lines), doc_lines / doc_line0 [D], hist [D][ncat], examples [D][ncat][3] fully
+ *   written; nbytes == 0 (text may be null) writes zeros (examples -1) and launches no kernel that
+ *   reads text.  tables_dev is read only. */
+#define KRCA_LOG_IMAGE_MAGIC 0x544C524Bu /* "KRLT" */
+#define KRCA_LOG_IMAGE_VERSION 1u
+#define KRCA_LOG_SYM_SEP 0xFFu
+#define KRCA_LOG_MAX_NCAT 16
+#define KRCA_LOG_MAX_NSYM 63
+#define KRCA_LOG_MAX_NSTATE 1024
+#define KRCA_LOG_MAX_NRANGE 1024
+#define KRCA_LOG_MAX_WARM 63
+typedef struct krca_log_dims {
+  int32_t ncat, nsym, nstate, nrange, warm, other;
+  uint64_t digest;
+} krca_log_dims;
+int krca_log_tables_check(const void* image_host, int64_t image_bytes, krca_log_dims* dims_host /*nullable*/);
+int64_t krca_log_tables_dev_size(const krca_log_dims* dims_host);
+int krca_log_tables_upload(const void* image_host, int64_t image_bytes, void* tables_dev, int64_t tables_dev_bytes,
+                           krca_log_dims* dims_host, void* stream);
+int krca_log_match_tables(const uint8_t* text, int64_t nbytes, const int64_t* doc_off, int64_t ndocs,
+                          int64_t* workspace, const void* tables_dev, int64_t tables_dev_bytes,
+                          const krca_log_dims* dims_host, int64_t n_lines,
+                          int64_t* line_start /*[L]*/, int64_t* line_end /*[L]*/, uint32_t* line_mask /*[L]*/,
+                          int32_t* doc_lines /*[D]*/, int32_t* hist /*[D][ncat]*/,
+                          int32_t* examples /*[D][ncat][3], nullable*/, int64_t* doc_line0 /*[D], nullable*/,
+                          void* stream);
+int krca_log_scan_tables(const uint8_t* text, int64_t nbytes, const int64_t* doc_off, int64_t ndocs,
+                         int64_t* workspace, const void* tables_dev, int64_t tables_dev_bytes,
+                         const krca_log_dims* dims_host, int64_t line_cap,
+                         int64_t* line_start /*[line_cap]*/, int64_t* line_end /*[line_cap]*/,
+                         uint32_t* line_mask /*[line_cap]*/, int32_t* doc_lines /*[D]*/, int32_t* hist /*[D][ncat]*/,
+                         int32_t* examples /*[D][ncat][3], nullable*/, int64_t* doc_line0 /*[D], nullable*/,
+                         int64_t* n_lines_host, void* stream);
+
 /* ---- a13: error-template hashing + per-container template histograms (new primitive) ------
  * template(line) = line bytes with every maximal [A-Za-z0-9_] run that contains an ASCII digit or
  * is >= 8 hex digits long replaced by the one byte 0xFF (shown as "<*>"; never in UTF-8 text);

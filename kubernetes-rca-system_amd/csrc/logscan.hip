@@ -27,9 +27,11 @@
 #include <cstdlib>
 
 #include <algorithm>
+#include <atomic>
 #include <type_traits>
 
 #include "krca_common.h"
+#include "log_rt_layout.h"
 #define KRCA_DFA_QUAL static __device__ __constant__ const
 #include "log_dfa_tables.h"
 
@@ -1715,6 +1717,8 @@ LogWs log_ws(int64_t* ws, int64_t nbytes) {
   return w;
 }
 
+#include "log_rt.h"  // the kernels over pattern tables compiled at run time
+
 }  // namespace
 
 extern "C" {
@@ -1857,6 +1861,116 @@ int krca_log_scan(const uint8_t* text, int64_t nbytes, const int64_t* doc_off, i
   hipLaunchKernelGGL(examples ? log_hist<true> : log_hist<false>, dim3((unsigned)krca::ceil_div(ndocs, TPB)), dim3(TPB),
                      0, st, doc_off, ndocs, (const int64_t*)w.chunk_line0, nt * TPB, line_start, line_mask, (int64_t)0, Ld,
                      line_cap, doc_lines, hist, examples, doc_line0);
+  KRCA_LAUNCH_CHECK();
+  KRCA_HIP(hipMemcpyAsync(n_lines_host, Ld, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  KRCA_HIP(hipStreamSynchronize(st));
+  return KRCA_OK;
+}
+
+// ---- pattern tables compiled at run time (include/krca.h) ------------------------------------------
+int krca_log_tables_upload(const void* image_host, int64_t image_bytes, void* tables_dev, int64_t tables_dev_bytes,
+                           krca_log_dims* dims_host, void* stream) {
+  KRCA_CHECK_ARG(tables_dev && dims_host, "krca_log_tables_upload: null pointer");
+  krca_log_dims d;
+  const int rc = krca_log_tables_check(image_host, image_bytes, &d);  // nothing is written when it fails
+  if (rc) return rc;
+  const krca::LogRtLayout l = krca::log_rt_layout(d);
+  KRCA_CHECK_ARG(tables_dev_bytes >= (int64_t)l.bytes, "krca_log_tables_upload: device buffer of %lld bytes, the tables need %u",
+                 (long long)tables_dev_bytes, l.bytes);
+  std::vector<uint8_t> form(l.bytes);
+  krca::log_tables_pack(image_host, d, form.data());
+  hipStream_t st = krca::as_stream(stream);
+  KRCA_HIP(hipMemcpyAsync(tables_dev, form.data(), l.bytes, hipMemcpyHostToDevice, st));
+  KRCA_HIP(hipStreamSynchronize(st));  // the staging copy lives until here
+  *dims_host = d;
+  return KRCA_OK;
+}
+
+int krca_log_match_tables(const uint8_t* text, int64_t nbytes, const int64_t* doc_off, int64_t ndocs, int64_t* ws,
+                          const void* tables_dev, int64_t tables_dev_bytes, const krca_log_dims* dims_host, int64_t n_lines,
+                          int64_t* line_start, int64_t* line_end, uint32_t* line_mask, int32_t* doc_lines, int32_t* hist,
+                          int32_t* examples, int64_t* doc_line0, void* stream) {
+  KRCA_CHECK_ARG(nbytes >= 0 && ndocs >= 1 && n_lines >= 0, "krca_log_match_tables: bad sizes");
+  KRCA_CHECK_ARG(doc_off && ws && doc_lines && hist, "krca_log_match_tables: null pointer");
+  KRCA_CHECK_ARG(((uintptr_t)text & 15) == 0, "krca_log_match_tables: text must be 16-byte aligned");
+  KRCA_CHECK_ARG(n_lines == 0 || (line_start && line_end && line_mask), "krca_log_match_tables: null line arrays");
+  hipStream_t st = krca::as_stream(stream);
+  RtPlan plan;
+  const int rc = rt_plan("krca_log_match_tables", tables_dev, tables_dev_bytes, dims_host, st, plan);
+  if (rc) return rc;
+  const uint8_t* tab = static_cast<const uint8_t*>(tables_dev);
+  const LogWs w = log_ws(ws, nbytes);
+  const int64_t nt = w.nt;
+  if (n_lines > 0) {
+    KRCA_HIP(hipMemsetAsync(w.n_long, 0, sizeof(int32_t), st));
+    hipLaunchKernelGGL(log_lines, dim3((unsigned)nt), dim3(TPB), 0, st, text, nbytes, doc_off, ndocs, (const int32_t*)w.cdoc,
+                       (const int32_t*)w.chunk, (const int64_t*)w.tile, n_lines, line_start, line_end, w.chunk_line0);
+    KRCA_LAUNCH_CHECK();
+    hipLaunchKernelGGL(log_last_end, dim3(1), dim3(1), 0, st, text, nbytes, doc_off, ndocs, n_lines,
+                       (const int64_t*)nullptr, (int64_t)0, line_end);
+    KRCA_LAUNCH_CHECK();
+    if (plan.rsl == 5)
+      rt_launch_walk<5>(plan, st, text, nbytes, n_lines, nullptr, 0, line_start, line_end, line_mask, w.long_q, w.n_long, tab);
+    else
+      rt_launch_walk<6>(plan, st, text, nbytes, n_lines, nullptr, 0, line_start, line_end, line_mask, w.long_q, w.n_long, tab);
+    KRCA_LAUNCH_CHECK();
+  } else {  // no lines: chunk_line0 = 0 for log_hist_rt
+    KRCA_HIP(hipMemsetAsync(w.chunk_line0, 0, nt * TPB * sizeof(int64_t), st));
+  }
+  hipLaunchKernelGGL(examples ? log_hist_rt<true> : log_hist_rt<false>, dim3((unsigned)krca::ceil_div(ndocs, TPB)),
+                     dim3(TPB), 0, st, doc_off, ndocs, (const int64_t*)w.chunk_line0, nt * TPB, line_start, line_mask, n_lines,
+                     (const int64_t*)nullptr, (int64_t)0, doc_lines, hist, examples, doc_line0, (int)plan.dm.ncat);
+  KRCA_LAUNCH_CHECK();
+  return KRCA_OK;
+}
+
+int krca_log_scan_tables(const uint8_t* text, int64_t nbytes, const int64_t* doc_off, int64_t ndocs, int64_t* ws,
+                         const void* tables_dev, int64_t tables_dev_bytes, const krca_log_dims* dims_host, int64_t line_cap,
+                         int64_t* line_start, int64_t* line_end, uint32_t* line_mask, int32_t* doc_lines, int32_t* hist,
+                         int32_t* examples, int64_t* doc_line0, int64_t* n_lines_host, void* stream) {
+  KRCA_CHECK_ARG(nbytes >= 0 && ndocs >= 1 && ndocs < INT32_MAX && line_cap >= 0, "krca_log_scan_tables: bad sizes");
+  KRCA_CHECK_ARG(doc_off && ws && doc_lines && hist && n_lines_host, "krca_log_scan_tables: null pointer");
+  KRCA_CHECK_ARG(nbytes == 0 || text, "krca_log_scan_tables: null text");
+  KRCA_CHECK_ARG(((uintptr_t)text & 15) == 0, "krca_log_scan_tables: text must be 16-byte aligned");
+  KRCA_CHECK_ARG(line_cap == 0 || (line_start && line_end && line_mask), "krca_log_scan_tables: null line arrays");
+  hipStream_t st = krca::as_stream(stream);
+  RtPlan plan;
+  const int rc = rt_plan("krca_log_scan_tables", tables_dev, tables_dev_bytes, dims_host, st, plan);
+  if (rc) return rc;
+  const uint8_t* tab = static_cast<const uint8_t*>(tables_dev);
+  const int ncat = plan.dm.ncat;
+  const LogWs w = log_ws(ws, nbytes);
+  const int64_t nt = w.nt;
+  int64_t* const tile = w.tile;
+  if (nbytes == 0) {  // no text (the pointer may be null): no kernel may read it; as krca_log_scan
+    KRCA_HIP(hipMemsetAsync(tile, 0, (nt + 1) * sizeof(int64_t), st));
+    KRCA_HIP(hipMemsetAsync(w.chunk_line0, 0, nt * TPB * sizeof(int64_t), st));
+    KRCA_HIP(hipMemsetAsync(doc_lines, 0, ndocs * sizeof(int32_t), st));
+    KRCA_HIP(hipMemsetAsync(hist, 0, ndocs * ncat * sizeof(int32_t), st));
+    if (examples) KRCA_HIP(hipMemsetAsync(examples, 0xFF, ndocs * ncat * 3 * sizeof(int32_t), st));  // -1
+    if (doc_line0) KRCA_HIP(hipMemsetAsync(doc_line0, 0, ndocs * sizeof(int64_t), st));
+    *n_lines_host = 0;
+    return KRCA_OK;
+  }
+  hipLaunchKernelGGL(log_chunk_doc, dim3((unsigned)krca::ceil_div(ndocs, TPB)), dim3(TPB), 0, st, doc_off, ndocs,
+                     nbytes, w.cdoc, w.status, 2 * nt + 1, w.n_long);  // the map; status words, ticket, long-line count zeroed
+  KRCA_LAUNCH_CHECK();
+  const int64_t* Ld = tile + nt;  // the line count, on the device
+  // always the two-pass path (KRCA_LOG_FUSED does not apply): the line index, then the walk re-reading the text
+  const int64_t resident = krca::resident_workgroups(reinterpret_cast<const void*>(&log_index_lines), TPB, st, 4);
+  const int64_t grid_ix = LOG_IDX_PERSIST ? std::min<int64_t>(nt, resident) : nt;
+  hipLaunchKernelGGL(log_index_lines, dim3((unsigned)grid_ix), dim3(TPB), 0, st, text, nbytes, doc_off, ndocs,
+                     (const int32_t*)w.cdoc, w.chunk, tile, w.status, w.ticket, nt, line_cap, line_start, line_end,
+                     w.chunk_line0, tile + nt);
+  KRCA_LAUNCH_CHECK();
+  if (plan.rsl == 5)
+    rt_launch_walk<5>(plan, st, text, nbytes, 0, Ld, line_cap, line_start, line_end, line_mask, w.long_q, w.n_long, tab);
+  else
+    rt_launch_walk<6>(plan, st, text, nbytes, 0, Ld, line_cap, line_start, line_end, line_mask, w.long_q, w.n_long, tab);
+  KRCA_LAUNCH_CHECK();
+  hipLaunchKernelGGL(examples ? log_hist_rt<true> : log_hist_rt<false>, dim3((unsigned)krca::ceil_div(ndocs, TPB)),
+                     dim3(TPB), 0, st, doc_off, ndocs, (const int64_t*)w.chunk_line0, nt * TPB, line_start, line_mask,
+                     (int64_t)0, Ld, line_cap, doc_lines, hist, examples, doc_line0, ncat);
   KRCA_LAUNCH_CHECK();
   KRCA_HIP(hipMemcpyAsync(n_lines_host, Ld, sizeof(int64_t), hipMemcpyDeviceToHost, st));
   KRCA_HIP(hipStreamSynchronize(st));

@@ -36,9 +36,22 @@ def format_examples(lines, n):
 
 
 class LogsAgent(BaseAgent):
-    def __init__(self, k8s_client, engine=None):
+    def __init__(self, k8s_client, engine=None, compile_patterns=False):
+        """compile_patterns: opt in to matching an EDITED ``error_patterns`` dict, as the reference does
+        (:20, :147-149): at analyze() time the dict's (name, regex) pairs are compiled into device tables
+        (krca/logdfa.py: fixed-length alternatives only; anything else gives the agent's error result).
+        Default False: an edited dict is refused, as before."""
         super().__init__(k8s_client, engine)
         self.error_patterns = dict(P.ERROR_PATTERNS)  # public attribute of the reference (:20)
+        self.compile_patterns = bool(compile_patterns)
+
+    def _runtime_tables(self):
+        """Device tables for an edited error_patterns under compile_patterns=True; None for the shipped
+        set (the compiled-in path) and whenever the opt-in is off."""
+        pats = list(self.error_patterns.items())
+        if not self.compile_patterns or pats == list(P.ERROR_PATTERNS):
+            return None
+        return self.engine.log_tables(pats)  # cached by digest; PatternsUnsupported -> the error result
 
     def _check_patterns_compiled(self):
         """The device matcher is compiled from krca/patterns.py (csrc/gen_log_dfa.py); the reference
@@ -87,13 +100,21 @@ class LogsAgent(BaseAgent):
                 deferred = e
 
             # (2) one device pass over all containers
+            tables, names = None, P.CATEGORY_NAMES
             if docs:
-                self._check_patterns_compiled()
-            scan = self.engine.log_scan(*pack_documents([d[3] for d in docs])) if docs else None
+                tables = self._runtime_tables()
+                if tables is None:
+                    self._check_patterns_compiled()
+                else:
+                    names = tuple(self.error_patterns)  # the dict's order and names
+            if tables is None:
+                scan = self.engine.log_scan(*pack_documents([d[3] for d in docs])) if docs else None
+            else:
+                scan = self.engine.log_scan(*pack_documents([d[3] for d in docs]), tables=tables)
 
             # (3) findings in the reference's order: per container, log findings then status
             for i, (pod, pod_name, cname, logs) in enumerate(docs):
-                self._report_container(scan, i, pod_name, cname)
+                self._report_container(scan, i, pod_name, cname, names)
                 self._check_container_status(pod, cname)
             if deferred is not None:
                 raise deferred
@@ -106,7 +127,7 @@ class LogsAgent(BaseAgent):
             return self._error_result("logs", e)
 
     # -- ref:agents/logs_agent.py:124-181 on device results -------------------------------
-    def _report_container(self, scan, d, pod_name, cname):
+    def _report_container(self, scan, d, pod_name, cname, names=P.CATEGORY_NAMES):
         n_lines = int(scan.n_lines[d])
         self.add_reasoning_step(observation=f"Analyzing {n_lines} log lines for {pod_name}/{cname}",
                                 conclusion="Beginning log pattern analysis")
@@ -115,7 +136,7 @@ class LogsAgent(BaseAgent):
             self.add_reasoning_step(observation=f"No error patterns detected in logs for {pod_name}/{cname}",
                                     conclusion="Container logs appear normal")
             return
-        for c, cat in enumerate(P.CATEGORY_NAMES):
+        for c, cat in enumerate(names):
             n = int(hist[c])
             if n == 0:
                 continue

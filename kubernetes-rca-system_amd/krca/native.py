@@ -47,6 +47,13 @@ SIGNATURES = {
                                c_vp]),
     "krca_log_scan": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                               c_vp, c_vp]),
+    "krca_log_tables_check": (c_i32, [c_vp, c_i64, c_vp]),
+    "krca_log_tables_dev_size": (c_i64, [c_vp]),
+    "krca_log_tables_upload": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp]),
+    "krca_log_match_tables": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp,
+                                      c_vp, c_vp, c_vp, c_vp]),
+    "krca_log_scan_tables": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp,
+                                     c_vp, c_vp, c_vp, c_vp, c_vp]),
     "krca_template_hash": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp]),
     "krca_template_hist_ws_size": (c_i64, [c_i64]),
     "krca_template_hist": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
@@ -136,6 +143,30 @@ class KrcaError(RuntimeError):
     pass
 
 
+class LogDims(ctypes.Structure):
+    """krca_log_dims of include/krca.h: the dimensions of one run-time pattern table."""
+    _fields_ = [("ncat", c_i32), ("nsym", c_i32), ("nstate", c_i32), ("nrange", c_i32), ("warm", c_i32),
+                ("other", c_i32), ("digest", ctypes.c_uint64)]
+
+
+class DeviceLogTables:
+    """A compiled pattern set on the device (NativeEngine.log_tables): the host tables
+    (krca.logdfa.LogTables), the device form and the dimensions the scan calls take."""
+
+    def __init__(self, tables, dev, dims):
+        self.tables, self.dev, self.dims = tables, dev, dims
+        self.ncat, self.names, self.digest = tables.ncat, tables.names, tables.digest
+
+
+def check_log_image(image, lib=None):
+    """krca_log_tables_check on a table image (host only, no GPU) -> LogDims; raises KrcaError."""
+    lib = lib or load_library()
+    dims = LogDims()
+    buf = (ctypes.c_char * len(image)).from_buffer_copy(image) if len(image) else None
+    _check(lib.krca_log_tables_check(buf, len(image), ctypes.byref(dims)), "krca_log_tables_check", lib)
+    return dims
+
+
 _lib = None
 
 
@@ -212,17 +243,18 @@ def check_doc_off(doc_off, nbytes):
         raise KrcaError("log scan: doc_off must be non-decreasing from 0 to len(text)")
 
 
-def example_ids(line_mask, doc_line0, doc_lines):
-    """[D, 13, 3] ids of the first three lines per container and category (-1 when fewer) from the
-    example bits of the line masks (bit 16 + c, include/krca.h krca_log_match); host numpy."""
+def example_ids(line_mask, doc_line0, doc_lines, ncat=NCAT):
+    """[D, ncat, 3] ids of the first three lines per container and category (-1 when fewer) from the
+    example bits of the line masks (bit 16 + c, include/krca.h krca_log_match); host numpy.
+    ncat: 13 for the compiled-in patterns, the tables' count for run-time tables."""
     lm = np.asarray(line_mask).view(np.uint32)
     D = len(doc_lines)
-    out = np.full((D, NCAT, 3), -1, np.int32)
+    out = np.full((D, ncat, 3), -1, np.int32)
     lines = np.flatnonzero(lm >> 16)
     if len(lines) == 0:
         return out
     doc = np.searchsorted(np.asarray(doc_line0, np.int64), lines, side="right") - 1
-    for c in range(NCAT):
+    for c in range(ncat):
         sel = ((lm[lines] >> (16 + c)) & 1).astype(bool)
         li, d = lines[sel], doc[sel]
         if len(li) == 0:
@@ -239,8 +271,8 @@ class LogScan:
     def __init__(self, blob, n_lines, hist, examples, line_start, line_end):
         self.blob = blob
         self.n_lines = n_lines          # int32[D]
-        self.hist = hist                # int32[D, 13]
-        self.example_ids = examples     # int32[D, 13, 3]
+        self.hist = hist                # int32[D, ncat] (13, or the run-time tables' count)
+        self.example_ids = examples     # int32[D, ncat, 3]
         self._start = line_start        # int64[ids] for the example ids only (dict)
         self._end = line_end
 
@@ -724,8 +756,31 @@ class NativeEngine:
                             f"{unicodedata.unidata_version}: regenerate csrc/log_dfa_tables.h "
                             f"(csrc/gen_log_dfa.py) for non-ASCII logs")
 
-    def log_scan_device(self, text, doc_off, validate=True, dense_examples=False):
+    def log_tables(self, patterns):
+        """Compile an ordered sequence of (name, regex) pairs (krca.logdfa.compile_patterns: raises
+        PatternsUnsupported outside the subset or the limits), validate the image and upload its
+        device form; cached per engine by pattern digest.  -> DeviceLogTables for ``tables=``."""
+        from . import logdfa
+        t = logdfa.compile_patterns(patterns)
+        cache = self.__dict__.setdefault("_log_tables", {})
+        hit = cache.get((t.digest, t.patterns))
+        if hit is not None:
+            return hit
+        image = t.image()
+        dims = check_log_image(image, self.lib)
+        dev = self.torch.empty(int(self.lib.krca_log_tables_dev_size(ctypes.byref(dims))), dtype=self.torch.uint8,
+                               device=self.device)
+        buf = (ctypes.c_char * len(image)).from_buffer_copy(image)
+        _check(self.lib.krca_log_tables_upload(buf, len(image), self.ptr(dev), dev.numel(), ctypes.byref(dims),
+                                               self._stream()), "krca_log_tables_upload")
+        cache[(t.digest, t.patterns)] = hit = DeviceLogTables(t, dev, dims)
+        return hit
+
+    def log_scan_device(self, text, doc_off, validate=True, dense_examples=False, tables=None):
         """text uint8 device tensor (16-byte aligned), doc_off int64 device tensor [D+1].
+        tables: a DeviceLogTables (log_tables()) to match a pattern set compiled at run time through
+        krca_log_scan_tables / krca_log_match_tables -- hist and examples then have tables.ncat
+        columns; None: the 13 compiled-in patterns, every code path as before.
         validate: check the doc_off contract on the device first (one stream sync); pass False only
         when the offsets were checked on the host (check_doc_off) before the upload.
         The example lines are marked in line_mask (bits 16-28, include/krca.h; example_ids() turns
@@ -742,26 +797,32 @@ class NativeEngine:
         st = self._stream()
         dl = torch.empty(D, dtype=torch.int32, device=self.device)
         d0 = torch.empty(D, dtype=torch.int64, device=self.device)
-        hist = torch.empty((D, NCAT), dtype=torch.int32, device=self.device)
-        ex = torch.empty((D, NCAT, 3), dtype=torch.int32, device=self.device) if dense_examples else None
+        ncat = NCAT if tables is None else tables.ncat
+        hist = torch.empty((D, ncat), dtype=torch.int32, device=self.device)
+        ex = torch.empty((D, ncat, 3), dtype=torch.int32, device=self.device) if dense_examples else None
         exp = self.ptr(ex) if ex is not None else None
+        if tables is not None:
+            scan_fn, match_fn = self.lib.krca_log_scan_tables, self.lib.krca_log_match_tables
+            targs = (self.ptr(tables.dev), tables.dev.numel(), ctypes.byref(tables.dims))
+        else:
+            scan_fn, match_fn, targs = self.lib.krca_log_scan, self.lib.krca_log_match, ()
         # one call (krca_log_scan) into line arrays of the capacity the last scan needed (+25 %);
         # a larger window falls through to krca_log_match with the index the call left in ws
         cap = max(self._log_cap, 1024)
         ls, le, lm = (torch.empty(cap, dtype=dt, device=self.device) for dt in (torch.int64, torch.int64, torch.int32))
         nh = c_i64(0)
-        _check(self.lib.krca_log_scan(self.ptr(text), nbytes, self.ptr(doc_off), D, self.ptr(ws), cap,
-                                      self.ptr(ls), self.ptr(le), self.ptr(lm), self.ptr(dl), self.ptr(hist),
-                                      exp, self.ptr(d0), ctypes.byref(nh), st), "krca_log_scan")
+        _check(scan_fn(self.ptr(text), nbytes, self.ptr(doc_off), D, self.ptr(ws), *targs, cap,
+                       self.ptr(ls), self.ptr(le), self.ptr(lm), self.ptr(dl), self.ptr(hist),
+                       exp, self.ptr(d0), ctypes.byref(nh), st), "krca_log_scan")
         L = int(nh.value)
         self._log_cap = max(self._log_cap, L + L // 4)
         if L > cap:
             ls = torch.empty(max(L, 1), dtype=torch.int64, device=self.device)
             le = torch.empty(max(L, 1), dtype=torch.int64, device=self.device)
             lm = torch.empty(max(L, 1), dtype=torch.int32, device=self.device)
-            _check(self.lib.krca_log_match(self.ptr(text), nbytes, self.ptr(doc_off), D, self.ptr(ws), L,
-                                           self.ptr(ls), self.ptr(le), self.ptr(lm), self.ptr(dl), self.ptr(hist),
-                                           exp, self.ptr(d0), st), "krca_log_match")
+            _check(match_fn(self.ptr(text), nbytes, self.ptr(doc_off), D, self.ptr(ws), *targs, L,
+                            self.ptr(ls), self.ptr(le), self.ptr(lm), self.ptr(dl), self.ptr(hist),
+                            exp, self.ptr(d0), st), "krca_log_match")
         return dict(n_lines_total=L, line_start=ls[:L], line_end=le[:L], line_mask=lm[:L], doc_lines=dl,
                     doc_line0=d0, hist=hist, examples=ex, text=text)
 
@@ -883,15 +944,18 @@ class NativeEngine:
             buf[:n] = torch.frombuffer(bytearray(blob), dtype=torch.uint8)
         return buf.to(self.device)[:n]
 
-    def log_scan(self, blob, doc_off):
+    def log_scan(self, blob, doc_off, tables=None):
+        """tables: as log_scan_device (LogScan.hist / example_ids then have tables.ncat columns)."""
         torch = self.torch
         doc_off = np.asarray(doc_off, dtype=np.int64)
         check_doc_off(doc_off, len(blob))
-        self.check_log_unicode(blob)
+        if tables is None:  # run-time tables were built by this interpreter: exact under its Unicode data
+            self.check_log_unicode(blob)
         text = self.upload_blob(blob)
         off = self._dev(doc_off)
-        r = self.log_scan_device(text, off, validate=False)
-        ex = example_ids(r["line_mask"].cpu().numpy(), r["doc_line0"].cpu().numpy(), r["doc_lines"].cpu().numpy())
+        r = self.log_scan_device(text, off, validate=False, tables=tables)
+        ex = example_ids(r["line_mask"].cpu().numpy(), r["doc_line0"].cpu().numpy(), r["doc_lines"].cpu().numpy(),
+                         NCAT if tables is None else tables.ncat)
         ids = np.unique(ex[ex >= 0]).astype(np.int64)
         starts, ends = {}, {}
         if len(ids):
