@@ -365,6 +365,49 @@ int krca_corr_prepare(const float* x, int64_t P, int32_t M, int32_t T, int32_t c
                       float* z32, uint16_t* zh, void* stream);
 int krca_corr_topk(const uint16_t* zh, const float* z32, int64_t P, int32_t T, int32_t k, double tau, void* cand,
                    int32_t* count, int32_t* out_idx, float* out_val, float* cert, void* stream);
+/* Lead/lag correlation along dependency edges (csrc/corr_edges.hip), single device,
+ * whole graph.  z float32 [N][T], pod-major, in the layout krca_corr_prepare writes as z32; the call
+ * standardises nothing itself (krca_corr_prepare scales a row to unit NORM, so that a dot product is
+ * r: for c_0 = r below, pass rows of unit variance, i.e. z32 times sqrt(T) -- the Python wrapper's
+ * corr_unit_variance_device).  The pull-CSR as krca_rca_precede takes it: row k = the callers j of
+ * k, edges j -> k.  L = max_lag, 0 <= L <= KRCA_CORR_MAX_LAG; tau >= 0; 0 <= slack <= L; mask uint8
+ * [N] or NULL.  For the edge at CSR position e, in row k with j = col[e], and each l in [-L, L]:
+ *   S_l = sum over t = max(0,-l) .. min(T, T-l) - 1  of  z[j][t+l] * z[k][t],      c_l = S_l / T
+ * (empty overlap, |l| >= T: 0).  For standardised rows c_0 is Pearson r and |c_l| <= 1 (the biased
+ * cross-correlation estimator); l > 0: the caller's series follows the dependency's by l steps.
+ * The reference evaluates this in float64 over the float32 inputs; the device accumulates S_l in
+ * float32 (fused multiply-adds) in a fixed order per edge with no float atomics -- two launches give
+ * the same bits -- and finishes with one correctly rounded division, (float)((double)S / (double)T).
+ * Per edge [E], fully written:  r0[e] = c_0;  lag[e] = the l of the largest |c_l| (compared as |S_l|),
+ * visiting 0, +1, -1, +2, -2, ... and replacing only on strictly greater (ties: the smaller |l|, then
+ * the positive l);  r_lag[e] = c_lag.  A self loop (j == k), an edge with mask[j] == 0 or
+ * mask[k] == 0, or a column outside [0, N) gets r0 = r_lag = 0, lag = 0 and is not classified.
+ * An edge is CORRELATED when fabsf(r_lag[e]) > tau (float32 compare of the stored value); a correlated
+ * edge is DEP_LEADS when lag > slack, CALLER_LEADS when lag < -slack, SYNC otherwise.
+ * Per caller j [N], over the rows j appears in: dep_lead[j], dep_sync[j] (counts), dep_best[j] = max
+ * over j's DEP_LEADS edges of ((int64)bits(|r_lag|) << 32) | (uint32)(0x7FFFFFFF - k): the strongest
+ * leading dependency, ties to the lower id; 0: none.  Per callee k [N]: caller_follow[k] (the
+ * DEP_LEADS edges of row k), caller_sync[k], caller_lead[k].  Integer counts and an integer max:
+ * independent of the schedule.  Rows of more than 512 callers are walked in 512-caller chunks by
+ * separate waves.  T + 2 L <= 16384 (a wave keeps the dependency's row in LDS); 16-byte loads when
+ * T % 4 == 0 and z is 16-byte aligned, 4-byte loads otherwise (same results).
+ * krca_corr_lead_key: key = (min(caller_follow, 2^20 - 1) << 32) | float bits of score for a pod with
+ * dep_lead == 0, caller_follow > 0 and score > 0 (a NaN score fails the compare), 0 for every other
+ * pod; feed it to krca_topk_i64, as krca_rca_first_mover_key's.
+ * Buffers: every output is fully written by the call: r0 / lag / r_lag [E] by the waves that walk the
+ * edges (masked rows included), dep_lead / dep_sync / dep_best [N] zeroed by the call and then updated
+ * with integer atomics, caller_* [N] stored for every row (chunks past the first add atomically
+ * afterwards); key [N] fully written.  ws: krca_corr_edges_ws_size(N, E) bytes, 8-byte aligned, no
+ * initialisation needed: {counter | chunk list}; the call zeroes the counter and reads only the list
+ * entries it appended.  Not for graph capture (memsets). */
+#define KRCA_CORR_MAX_LAG 16
+int64_t krca_corr_edges_ws_size(int64_t N, int64_t E);
+int krca_corr_edges(const float* z, int64_t N, int32_t T, const int64_t* row_ptr, const int32_t* col, int32_t max_lag,
+                    float tau, int32_t slack, const uint8_t* mask /*[N] or NULL*/, float* r0 /*[E]*/,
+                    int8_t* lag /*[E]*/, float* r_lag /*[E]*/, int32_t* dep_lead, int32_t* dep_sync, int64_t* dep_best,
+                    int32_t* caller_follow, int32_t* caller_sync, int32_t* caller_lead, void* ws, void* stream);
+int krca_corr_lead_key(const int32_t* dep_lead, const int32_t* caller_follow, const float* score, int64_t N,
+                       int64_t* key, void* stream);
 /* a9 pod-sharded (kubernetes-rca-system_amd/krca/corr_dist.py): rank g of G owns pods
  * [lo, lo + n_loc), lo a multiple of 256; zh / z32 / phi are the all-gathered full arrays.  The
  * upper triangle is split by super-tile (every G-th from g); candidates travel to their pod's

@@ -22,11 +22,17 @@ from .traces import TracesAgent
 
 
 class Coordinator:
-    def __init__(self, k8s_client, engine=None, rank_config=None):
+    def __init__(self, k8s_client, engine=None, rank_config=None, correlations=False, corr_channel=0, corr_span=None,
+                 corr_max_lag=8, corr_tau=0.5, corr_slack=0):
         from krca.rca import RANKING
         self.k8s_client = k8s_client
         self._engine = engine
         self.rank_config = rank_config or RANKING
+        # correlations=True: the comprehensive result gains the additive key "correlations" (lead/lag
+        # correlation of metric channel corr_channel along the dependency edges, krca_corr_edges)
+        self.correlations = bool(correlations)
+        self.corr_params = {'channel': int(corr_channel), 'span': None if corr_span is None else int(corr_span),
+                            'max_lag': int(corr_max_lag), 'tau': float(corr_tau), 'slack': int(corr_slack)}
         self.metrics_agent = MetricsAgent(k8s_client, engine, window=self.rank_config.window,
                                           z_threshold=self.rank_config.z_threshold)
         self.logs_agent = LogsAgent(k8s_client, engine)
@@ -73,6 +79,10 @@ class Coordinator:
         ranked = self._rank_root_causes(namespace)
         if ranked is not None:
             out['ranked_root_causes'] = ranked
+        if self.correlations:
+            corr = self._correlations(namespace, ranked)
+            if corr is not None:
+                out['correlations'] = corr
         return out
 
     def _correlate_findings(self, *lists):  # ref :118-155
@@ -120,6 +130,33 @@ class Coordinator:
     def _reset_agents(self):
         for a in (self.metrics_agent, self.logs_agent, self.traces_agent, self.topology_agent, self.events_agent):
             a.reset()
+
+    # -- additive lead/lag correlations ------------------
+    def _correlations(self, namespace, ranked):
+        """lead_roots: anomalous pods that follow none of their dependencies and are followed by
+        callers (ranked by those callers, then by anomaly); followers: per ranked root cause with a
+        leading dependency, the strongest one, its lead in steps and r.  None without the bulk
+        accessors (get_pod_metric_tensor and get_dependency_csr)."""
+        from krca.leadlag import follower
+        c = self.k8s_client
+        scores = self.metrics_agent.last_scores
+        if scores is None or not hasattr(c, 'get_pod_metric_tensor') or not hasattr(c, 'get_dependency_csr'):
+            return None
+        names, row_ptr, col, _ = c.get_dependency_csr(namespace)
+        _, x = c.get_pod_metric_tensor(namespace)
+        p = self.corr_params
+        span = p['span'] if p['span'] is None else min(p['span'], int(x.shape[0]))
+        edges = self.engine.corr_edges(x, row_ptr, col, channel=p['channel'], span=span, max_lag=p['max_lag'],
+                                       tau=p['tau'], slack=p['slack'], host=False)
+        index = {f"Pod/{n}": i for i, n in enumerate(names)}
+        pods = [index[r['component']] for r in (ranked or []) if r['component'] in index]
+        lr = self.engine.lead_roots(edges, scores['score'], k=min(int(self.rank_config.k), 16), explain=pods,
+                                    row_ptr=row_ptr, col=col)
+        roots = [{'component': f"Pod/{names[i]}", 'rank': r + 1, 'followers': int(f), 'anomaly': float(s)}
+                 for r, (i, f, s) in enumerate(zip(lr['idx'].tolist(), lr['followers'].tolist(), lr['score'].tolist()))]
+        foll = [follower(names[i], names[lr['explained'][i][0]], lr['explained'][i][1], lr['explained'][i][2])
+                for i in pods if i in lr['explained']]
+        return {'lead_roots': roots, 'followers': foll, 'params': dict(p)}
 
     # -- additive ranking ----------------------------------------------------------------
     def _rank_root_causes(self, namespace):

@@ -68,6 +68,10 @@ SIGNATURES = {
     "krca_corr_eps": (c_f32, [c_i32]),
     "krca_corr_prepare": (c_i32, [c_vp, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "krca_corr_topk": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_i32, c_f64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "krca_corr_edges_ws_size": (c_i64, [c_i64, c_i64]),
+    "krca_corr_edges": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp, c_i32, c_f32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "krca_corr_lead_key": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp]),
     "krca_corr_shard_ws_size": (c_i64, [c_i64, c_i32, c_i32, c_i64, c_i32]),
     "krca_corr_shard_sample": (c_i32, [c_vp, c_i64, c_i32, c_i32, c_i64, c_i64, c_i32, c_vp, c_vp, c_vp]),
     "krca_corr_shard_tiles": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_i32, c_f64, c_i32, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp,
@@ -935,6 +939,113 @@ class NativeEngine:
         x = self._dev(x, self.torch.float32)
         r = self.corr_topk_device(self.corr_prepare_device(x, channel), k, tau)
         return {key: v.cpu().numpy() for key, v in r.items()}
+
+    # -- a9e: lead/lag correlation along dependency edges (csrc/corr_edges.hip) ------
+    CORR_EDGE_KEYS = ("r0", "lag", "r_lag")
+    CORR_POD_KEYS = ("dep_lead", "dep_sync", "dep_best", "caller_follow", "caller_sync", "caller_lead")
+
+    def corr_edges_device(self, z32, row_ptr, col, max_lag=8, tau=0.5, slack=0, mask=None):
+        """krca_corr_edges over the whole pull-CSR (device tensors; z32 float32 [N, T] pod-major, rows
+        of unit variance as corr_unit_variance_device gives them -- the call standardises nothing;
+        mask uint8 [N] or None) -> dict of device tensors: r0, r_lag
+        float32 [E], lag int8 [E]; dep_lead, dep_sync, caller_follow, caller_sync, caller_lead int32
+        [N]; dep_best int64 [N]."""
+        torch = self.torch
+        N, T = int(z32.shape[0]), int(z32.shape[1])
+        if int(row_ptr.numel()) != N + 1:
+            raise KrcaError(f"corr_edges: row_ptr has {int(row_ptr.numel())} entries for {N} pods")
+        if z32.dtype != torch.float32 or not z32.is_contiguous():
+            raise KrcaError("corr_edges: z32 must be a contiguous float32 [N, T] tensor")
+        if mask is not None and (mask.dtype != torch.uint8 or int(mask.numel()) != N):
+            raise KrcaError(f"corr_edges: mask must be uint8 [{N}]")
+        E = int(row_ptr[N].item())
+        if E > int(col.numel()):
+            raise KrcaError(f"corr_edges: row_ptr ends at {E} but col has {int(col.numel())} entries")
+        new = lambda dt, n: torch.empty(max(n, 1), dtype=dt, device=self.device)  # noqa: E731  (E = 0: one spare slot)
+        out = dict(r0=new(torch.float32, E), lag=new(torch.int8, E), r_lag=new(torch.float32, E))
+        for key in self.CORR_POD_KEYS:
+            out[key] = new(torch.int64 if key == "dep_best" else torch.int32, N)
+        ws = self._workspace("corr_edges", self.lib.krca_corr_edges_ws_size(N, E))
+        _check(self.lib.krca_corr_edges(self.ptr(z32), N, T, self.ptr(row_ptr), self.ptr(col), int(max_lag), float(tau),
+                                        int(slack), self.ptr(mask) if mask is not None else None, self.ptr(out["r0"]),
+                                        self.ptr(out["lag"]), self.ptr(out["r_lag"]), self.ptr(out["dep_lead"]),
+                                        self.ptr(out["dep_sync"]), self.ptr(out["dep_best"]),
+                                        self.ptr(out["caller_follow"]), self.ptr(out["caller_sync"]),
+                                        self.ptr(out["caller_lead"]), self.ptr(ws), self._stream()), "krca_corr_edges")
+        for key in self.CORR_EDGE_KEYS:
+            out[key] = out[key][:E]
+        return out
+
+    def corr_unit_variance_device(self, x, channel=0):
+        """x float32 [T, P, M] on the device -> float32 [P, T] rows of zero mean and unit population
+        variance (a flat row: zeros), the input krca_corr_edges reads c_0 = S_0 / T as Pearson r on.
+        krca_corr_prepare scales its z32 rows to unit norm (1 / (std sqrt(T)), so that a dot product
+        is r); this is that buffer times sqrt(T), in place."""
+        z32 = self.corr_prepare_device(x, channel)["z32"]
+        return z32.mul_(float(np.sqrt(np.float64(z32.shape[1]))))
+
+    def corr_edges(self, x, row_ptr, col, channel=0, span=None, max_lag=8, tau=0.5, slack=0, mask=None, host=True):
+        """x [T, P, M] (host or device) -> dict of host arrays (see corr_edges_device; host=False: the
+        device tensors, no copy).  span: correlate only the last `span` steps (x[T - span:] is
+        contiguous in this layout); the series are standardised over those steps
+        (corr_unit_variance_device)."""
+        torch = self.torch
+        x = self._dev(x, torch.float32)
+        if span is not None:
+            span = int(span)
+            if not 1 <= span <= x.shape[0]:
+                raise KrcaError(f"corr_edges: span {span} outside [1, {x.shape[0]}]")
+            x = x[x.shape[0] - span:]
+        rp, cl = self._csr_dev(row_ptr, col)
+        if mask is not None:
+            mask = self._dev(mask, torch.uint8) if isinstance(mask, torch.Tensor) else self._dev(np.asarray(mask, np.uint8))
+        out = self.corr_edges_device(self.corr_unit_variance_device(x, channel), rp, cl, max_lag, tau, slack, mask)
+        return {key: v.cpu().numpy() for key, v in out.items()} if host else out
+
+    def corr_lead_key_device(self, edges_out, score):
+        torch = self.torch
+        N = int(score.numel())
+        key = torch.empty(N, dtype=torch.int64, device=self.device)
+        _check(self.lib.krca_corr_lead_key(self.ptr(edges_out["dep_lead"]), self.ptr(edges_out["caller_follow"]),
+                                           self.ptr(score), N, self.ptr(key), self._stream()), "krca_corr_lead_key")
+        return key
+
+    def lead_roots(self, edges_out, score, k=10, explain=(), row_ptr=None, col=None):
+        """The lead roots of a corr_edges_device result: pods with a positive `score` (float32 [N], e.g.
+        the anomaly score) that follow none of their dependencies and are followed by at least one
+        caller, ranked by those callers, then by score.  -> dict of host arrays over the selected pods
+        (at most k <= 16, krca_topk_i64's limit): idx, followers, score; `explained` maps each pod of
+        `explain` with a leading dependency to (that dependency -- the strongest |r|, then the lowest
+        id --, its lead in steps, r); the lag and r are looked up in the per-edge arrays on the host, which
+        needs the CSR (host or device `row_ptr`, `col`)."""
+        torch = self.torch
+        dev = {key: (v if isinstance(v, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(v))).to(self.device)
+               for key, v in edges_out.items()}
+        sc = self._dev(score, torch.float32) if isinstance(score, torch.Tensor) else \
+            self._dev(np.asarray(score, np.float32))
+        N = int(sc.numel())
+        key = self.corr_lead_key_device(dev, sc)
+        idx, val = self.topk_device(key, min(int(k), N))
+        idx, val = idx.cpu().numpy(), val.cpu().numpy()
+        idx = idx[val > 0].astype(np.int64)
+        sel = torch.from_numpy(idx).to(self.device)
+        take = lambda t: t.index_select(0, sel).cpu().numpy()  # noqa: E731
+        res = dict(idx=idx.astype(np.int32), followers=take(dev["caller_follow"]), score=take(sc), explained={})
+        pods = np.asarray(list(explain), np.int64)
+        if len(pods):
+            from .leadlag import decode_dep_best, edge_of
+            if row_ptr is None or col is None:
+                raise KrcaError("lead_roots: explain needs row_ptr and col")
+            best = dev["dep_best"].index_select(0, torch.from_numpy(pods).to(self.device)).cpu().numpy()
+            rp = np.asarray(row_ptr.cpu() if isinstance(row_ptr, torch.Tensor) else row_ptr, np.int64)
+            cl = np.asarray(col.cpu() if isinstance(col, torch.Tensor) else col, np.int32)
+            lag, r_lag = dev["lag"].cpu().numpy(), dev["r_lag"].cpu().numpy()
+            for p, b in zip(pods.tolist(), best.tolist()):
+                dep = decode_dep_best(b)
+                if dep is not None:
+                    e = edge_of(rp, cl, lag, r_lag, p, dep[0], dep[2])
+                    res["explained"][p] = (dep[0], int(lag[e]), float(r_lag[e]))
+        return res
 
     def upload_blob(self, blob):
         torch = self.torch
