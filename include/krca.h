@@ -740,7 +740,35 @@ int krca_group_reduce(const int32_t* slot, const int64_t* key, int64_t N, int64_
  *   written when *n_edges_host <= cap, nothing past edge_key[cap - 1] ever.  krca_trace_stats:
  *   accumulate == 0 zeroes rec [S][8] and hist [S][NB] itself; accumulate != 0 adds into them, so the
  *   CALLER zeroes them before the first window.  krca_trace_quantiles writes out [S][Q] fully.
- *   Except for that accumulate form, no initialisation needed. */
+ *   Except for that accumulate form, no initialisation needed.
+ *
+ * krca_trace_critical: which of a span's microseconds its request was waiting for.  start_us (any common
+ *   origin) adds the one input the calls above lack: span i occupies [s_i, e_i), e_i = s_i + dur_us[i], in
+ *   64 bits.  A span is BAD if svc is outside [0, S) (as in link) or start_us outside [-2^62, 2^62): its
+ *   outputs are 0, it is nobody's child and nobody's valid parent, and it is counted in the first int64
+ *   of ws.  A parent is VALID as in link (in range, not the span itself, not bad); a span that is not bad
+ *   and has no valid parent is a ROOT.
+ *   Sweep of a span p over its valid children: child c is clipped to cs = max(s_c, s_p),
+ *   ce = min(e_c, e_p); a child with ce <= cs is never selected.  cursor = e_p; among the children with
+ *   ce <= cursor the one with the largest ce (ties: smallest cs, then lowest span index) is SELECTED,
+ *   cursor = cs; repeat until no child qualifies (a child still running at the cursor was hidden behind
+ *   the one chosen; every selection lowers the cursor, so no child is selected twice).
+ *   A root is ON THE PATH.  A non-root is on the path iff for some k <= D = krca_trace_critical_max_depth()
+ *   = 4096 its k-th valid ancestor is a root and the span and every ancestor below that root are
+ *   SELECTED: parent cycles and spans deeper than D are off the path.
+ *   path[i]: bit 0 = SELECTED, bit 1 = on the path, bit 2 = root.  crit_us[i] = dur_us[i] - sum of
+ *   (ce - cs) over the SELECTED children if the span is on the path, else 0 (the pieces are disjoint and
+ *   inside the span: no clamp).  Where every child's interval lies inside its parent's, the crit_us of a
+ *   trace sum to its root's dur_us exactly; a child that overruns its parent keeps its full own time, so
+ *   the sum then exceeds the root's duration.
+ *   Parents with at most krca_trace_critical_small_max() children are swept by one lane each, heavier
+ *   ones by one workgroup each: same bits.  Both helpers and krca_trace_critical_ws_size are host
+ *   functions without device work.  No host synchronisation, no allocation.
+ * Buffers: crit_us [N] and path [N] are written for every i.  ws: krca_trace_critical_ws_size(N) bytes,
+ *   8-byte aligned = {8 counters | clipped child intervals | valid parent | child count | list cursor |
+ *   child index | heavy parents | scan tile sums | selected}: counters and counts zeroed by the call,
+ *   every other word written before it is read (the heavy list only up to its counter).  No
+ *   initialisation needed. */
 int32_t krca_trace_nbuckets(void);
 int32_t krca_trace_bucket(uint32_t d);
 int krca_trace_bucket_bounds(int32_t b, uint32_t* lo_host, uint32_t* hi_host);
@@ -755,6 +783,11 @@ int krca_trace_stats(const int32_t* slot, const uint32_t* val, const uint8_t* fl
                      int32_t accumulate, int64_t* rec, uint32_t* hist, void* stream);
 int krca_trace_quantiles(const int64_t* rec, const uint32_t* hist, int32_t S, const int32_t* permille_host, int32_t Q,
                          uint32_t* out, void* stream);
+int32_t krca_trace_critical_max_depth(void);
+int32_t krca_trace_critical_small_max(void);
+int64_t krca_trace_critical_ws_size(int64_t N);
+int krca_trace_critical(const int32_t* svc, const int32_t* parent, const int64_t* start_us, const uint32_t* dur_us,
+                        int64_t N, int32_t S, uint32_t* crit_us, uint8_t* path, void* ws, void* stream);
 
 #ifdef __cplusplus
 }

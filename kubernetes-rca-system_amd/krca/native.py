@@ -136,6 +136,10 @@ SIGNATURES = {
     "krca_trace_edges": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_i64, c_vp, c_vp, c_vp, ctypes.POINTER(c_i64), c_vp]),
     "krca_trace_stats": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "krca_trace_quantiles": (c_i32, [c_vp, c_vp, c_i32, ctypes.POINTER(c_i32), c_i32, c_vp, c_vp]),
+    "krca_trace_critical_max_depth": (c_i32, []),
+    "krca_trace_critical_small_max": (c_i32, []),
+    "krca_trace_critical_ws_size": (c_i64, [c_i64]),
+    "krca_trace_critical": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp]),
 }
 
 KRCA_ENOTCONV = -70
@@ -700,9 +704,31 @@ class NativeEngine:
         q = self.trace_quantiles_device(rec, hist, S, permille)
         return rec[:S].cpu().numpy(), hist[:S].cpu().numpy().view(np.uint32), q[:S].cpu().numpy().view(np.uint32)
 
+    def trace_critical_device(self, svc, parent, start, dur, N, S):
+        """-> (crit_us int32 (uint32 bits), path uint8, ws) device tensors (csrc/trace_critical.hip);
+        ws's first int64 is the number of bad spans once the stream has run."""
+        torch = self.torch
+        n1 = max(int(N), 1)
+        crit = torch.empty(n1, dtype=torch.int32, device=self.device)
+        path = torch.empty(n1, dtype=torch.uint8, device=self.device)
+        ws = torch.empty(int(self.lib.krca_trace_critical_ws_size(N)) // 8, dtype=torch.int64, device=self.device)
+        _check(self.lib.krca_trace_critical(self.ptr(svc), self.ptr(parent), self.ptr(start), self.ptr(dur), int(N),
+                                            int(S), self.ptr(crit), self.ptr(path), self.ptr(ws), self._stream()),
+               "krca_trace_critical")
+        return crit, path, ws
+
+    def trace_critical(self, svc, parent, start_us, dur_us, S):
+        """Host arrays -> (crit_us uint32[N], path uint8[N], n_bad)."""
+        N = len(svc)
+        c, p, ws = self.trace_critical_device(self._dev_n(svc, np.int32), self._dev_n(parent, np.int32),
+                                              self._dev_n(start_us, np.int64), self._dev_n(dur_us, np.uint32), N, S)
+        return c[:N].cpu().numpy().view(np.uint32), p[:N].cpu().numpy(), int(ws[0].item())
+
     def trace_analyze(self, cols):
         """SpanColumns -> tracecols.TraceStats: link, edges, then per service (duration and self
-        time), per call edge and per operation: records + 500 / 900 / 950 / 990 permille."""
+        time), per call edge and per operation: records + 500 / 900 / 950 / 990 permille.  Columns
+        with ``start_us`` add the critical path: krca_trace_critical, then the critical time of the
+        spans on the path per service and per call edge through the same stats / quantiles calls."""
         from . import tracecols
         torch = self.torch
         N, S, n_ops = len(cols), len(cols.services), len(cols.ops)
@@ -719,7 +745,19 @@ class NativeEngine:
             rec, hist = self.trace_stats_device(slot, val, flags, N, n_slots)
             q = self.trace_quantiles_device(rec, hist, n_slots, tracecols.PERMILLE)
             out[name] = (rec[:n_slots].cpu().numpy(), q[:n_slots].cpu().numpy().view(np.uint32))
-        return tracecols.TraceStats(cols.services, cols.ops, N, n_bad, edge_key.cpu().numpy(), out)
+        n_roots = None
+        start = getattr(cols, "start_us", None)
+        if start is not None:
+            crit, path, _ = self.trace_critical_device(svc, parent, self._dev_n(start, np.int64), dur, N, S)
+            on = (path & 2) != 0
+            off_path = torch.full_like(svc, -1)
+            for name, slot, n_slots in (("crit", torch.where(on, svc, off_path), S),
+                                        ("critedge", torch.where(on, edge_slot, off_path), E)):
+                rec, hist = self.trace_stats_device(slot, crit, flags, N, n_slots)
+                q = self.trace_quantiles_device(rec, hist, n_slots, tracecols.PERMILLE)
+                out[name] = (rec[:n_slots].cpu().numpy(), q[:n_slots].cpu().numpy().view(np.uint32))
+            n_roots = int(((path[:N] & 4) != 0).sum().item())
+        return tracecols.TraceStats(cols.services, cols.ops, N, n_bad, edge_key.cpu().numpy(), out, n_roots)
 
     # -- top-k -------------------------------------------------------------------------------
     def topk_device(self, v, k):

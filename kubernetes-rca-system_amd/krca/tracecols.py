@@ -12,6 +12,8 @@ Columns (``SpanColumns``), one entry per span, ids into per-column tables:
   svc int32 (service that executed the span), parent int32 (index of the parent span in this table;
   -1 = root, or a parent outside the window), op int32 (interned (service, operation name) pair;
   ``ops = [(svc_id, name)]``), dur_us uint32, err uint8 (0 / 1).  Tables: ``services``, ``ops``.
+  Optional: start_us int64 (any common origin).  With it ``trace_analyze`` also extracts the critical
+  path of every trace (krca_trace_critical): which service each request was waiting on.
 """
 import numpy as np
 
@@ -21,6 +23,7 @@ EDGE_P95_US = 200_000         # "high latency (>200ms) in calls from service_a t
 ERROR_RATE_PCT = 5            # "5% of traces show HTTP 500"
 DEPENDENCY_SHARE = 0.5        # an edge carrying more than half of a caller's outgoing calls ...
 DEPENDENCY_MIN_CALLEES = 2    # ... of a caller with at least two callees
+CRITICAL_SHARE = 0.25         # a service holding more than a quarter of all critical-path time
 TOP_FINDINGS = 20             # findings emitted per analysis (the total goes in the reasoning step)
 PERMILLE = (500, 900, 950, 990)
 Q50, Q90, Q95, Q99 = range(4)
@@ -32,12 +35,13 @@ class SpanColumns:
     """Columnar spans (see module docstring).  ``services`` is a list of str, ``ops`` a list of
     (service id, operation name)."""
 
-    def __init__(self, svc, parent, op, dur_us, err, services, ops, has_parents=True):
+    def __init__(self, svc, parent, op, dur_us, err, services, ops, has_parents=True, start_us=None):
         self.svc, self.parent = np.asarray(svc, np.int32), np.asarray(parent, np.int32)
         self.op, self.dur_us = np.asarray(op, np.int32), np.asarray(dur_us, np.uint32)
         self.err = np.asarray(err, np.uint8)
         self.services, self.ops = list(services), list(ops)
         self.has_parents = has_parents  # some span carried a parentId (encode_spans)
+        self.start_us = None if start_us is None else np.asarray(start_us, np.int64)  # switches the critical path on
 
     def __len__(self):
         return len(self.svc)
@@ -51,9 +55,11 @@ def encode_spans(traces):
     """Trace dicts shaped like get_trace_details (``spans: [{id, name, service, duration, error}]``
     plus an optional ``parentId``; duration in ms) -> SpanColumns, or None when a value is not a
     plain str / int / bool.  Parent ids resolve to indices within their trace; an unknown parent id
-    is a parent outside the window (-1)."""
+    is a parent outside the window (-1).  ``start_us`` is filled when EVERY span carries an integer
+    ``startTime`` (ms, as duration) inside +-2^62 us; otherwise it stays None."""
     svc_t, op_t = {}, {}
     svc, op, dur, err, pid, index = [], [], [], [], [], {}
+    start, has_starts = [], True
     has_parents = False
     if type(traces) not in (list, tuple):
         return None
@@ -72,6 +78,11 @@ def encode_spans(traces):
             if p is not None and type(p) not in (str, int):
                 return None
             has_parents = has_parents or 'parentId' in sp
+            st = sp.get('startTime')
+            if has_starts and type(st) is int and -2 ** 62 <= st * 1000 < 2 ** 62:
+                start.append(st * 1000)
+            else:
+                has_starts = False
             s = svc_t.setdefault(service, len(svc_t))
             index[(t, sid)] = len(svc)
             svc.append(s)
@@ -80,7 +91,8 @@ def encode_spans(traces):
             err.append(1 if e else 0)
             pid.append(None if p is None else (t, p))
     parent = [-1 if p is None else index.get(p, -1) for p in pid]
-    return SpanColumns(svc, parent, op, dur, err, list(svc_t), list(op_t), has_parents)
+    return SpanColumns(svc, parent, op, dur, err, list(svc_t), list(op_t), has_parents,
+                       start if has_starts and svc else None)
 
 
 def make_spans(n_traces, n_services, seed=0, depth=4, max_calls=3, fanout=3, ops_per_service=3,
@@ -159,19 +171,97 @@ def make_spans(n_traces, n_services, seed=0, depth=4, max_calls=3, fanout=3, ops
     return cols, dict(slow=int(slow_service), origin=int(origin_service))
 
 
+def span_depths(parent):
+    """Depth of every span of a parent FOREST (roots = -1 or out of range: depth 0); ValueError on a
+    parent cycle."""
+    parent = np.asarray(parent, np.int64)
+    N = len(parent)
+    has = (parent >= 0) & (parent < N) & (parent != np.arange(N))
+    depth = np.where(has, -1, 0)
+    todo = np.flatnonzero(has)
+    while len(todo):
+        d = depth[parent[todo]]
+        done = d >= 0
+        if not done.any():
+            raise ValueError("span_depths: the parent links hold a cycle")
+        depth[todo[done]] = d[done] + 1
+        todo = todo[~done]
+    return depth
+
+
+def add_starts(cols, seed=0, p_parallel=0.0, window_us=600_000_000):
+    """SpanColumns (a parent forest, as make_spans gives) -> new SpanColumns with ``start_us`` set so
+    that every child's interval lies inside its parent's.  A span's self time is recovered as
+    dur - sum of its children's.  A parent drawn "parallel" (probability ``p_parallel``) starts all its
+    children together after a head gap, and its duration becomes self + the longest child (durations
+    are recomputed bottom-up, so ``dur_us`` shrinks on those chains); the others run their children
+    back to back in span order with the self time split into the gaps before, between and after
+    them.  Root starts are spread over ``window_us``.  Draws are independent of make_spans'."""
+    rng = np.random.default_rng(seed)
+    N = len(cols)
+    parent = np.asarray(cols.parent, np.int64)
+    has = (parent >= 0) & (parent < N) & (parent != np.arange(N))
+    depth = span_depths(parent)
+    kids = np.flatnonzero(has)
+    kpar = parent[kids]
+    dur = np.asarray(cols.dur_us, np.int64).copy()
+    child_sum = np.zeros(N, np.int64)
+    np.add.at(child_sum, kpar, dur[kids])
+    self_us = np.maximum(dur - child_sum, 0)
+    parallel = rng.random(N) < p_parallel
+    levels = [np.flatnonzero(has & (depth == d)) for d in range(1, int(depth.max(initial=0)) + 1)]
+    for lv in reversed(levels):  # children before parents: dur = self + (longest | all) children
+        acc_sum, acc_max = np.zeros(N, np.int64), np.zeros(N, np.int64)
+        np.add.at(acc_sum, parent[lv], dur[lv])
+        np.maximum.at(acc_max, parent[lv], dur[lv])
+        ps = np.unique(parent[lv])
+        dur[ps] = self_us[ps] + np.where(parallel[ps], acc_max[ps], acc_sum[ps])
+    if N and int(dur.max()) >= 2 ** 32:  # only where children outlast a parent whose duration was capped
+        raise ValueError("add_starts: a recomputed duration does not fit dur_us (uint32)")
+    # gaps: integer shares of the parent's self time, one weight per child and one for the tail
+    order = kids[np.lexsort((kids, kpar))]  # by parent, then span index
+    opar = parent[order]
+    weight = rng.integers(1, 1025, len(order))
+    tail_w = rng.integers(1, 1025, N)
+    wsum = tail_w.copy()
+    np.add.at(wsum, opar, weight)
+    gap = self_us[opar] * weight // wsum[opar]  # floors: their sum stays within the self time
+    first = np.ones(len(order), bool)
+    first[1:] = opar[1:] != opar[:-1]
+    run = np.cumsum(gap + dur[order]) - dur[order]  # gaps so far + the earlier siblings' durations
+    head = np.maximum.accumulate(np.where(first, np.arange(len(order)), 0)) if len(order) else first.astype(np.int64)
+    base = (run - gap)[head]  # the running total before each group's first child
+    seq_off = run - base
+    offset = np.zeros(N, np.int64)
+    offset[order] = np.where(parallel[opar], gap[head], seq_off)
+    start = np.zeros(N, np.int64)
+    roots = np.flatnonzero(~has)
+    start[roots] = rng.integers(0, max(int(window_us), 1), len(roots))
+    for lv in levels:  # parents before children
+        start[lv] = start[parent[lv]] + offset[lv]
+    return SpanColumns(cols.svc, cols.parent, cols.op, dur, cols.err, cols.services, cols.ops,
+                       getattr(cols, "has_parents", True), start)
+
+
 class TraceStats:
     """Results of ``engine.trace_analyze``: per service (``svc`` on duration, ``self`` on self
     time), per call edge (``edge``) and per operation (``op``) the (rec int64 [n, 8], q uint32
     [n, 4]) arrays of krca_trace_stats / krca_trace_quantiles, the ascending edge keys
-    caller * S + callee, and the reference's four trace schemas built from them."""
+    caller * S + callee, and the reference's four trace schemas built from them.  Columns with
+    ``start_us`` add ``crit`` (per service) and ``critedge`` (per call edge) on the critical time of
+    the spans on the critical path (krca_trace_critical) and ``n_roots``; absent otherwise."""
 
-    def __init__(self, services, ops, n_spans, n_bad, edge_key, tables):
+    def __init__(self, services, ops, n_spans, n_bad, edge_key, tables, n_roots=None):
         self.services, self.ops = list(services), list(ops)
         self.n_spans, self.n_bad = int(n_spans), int(n_bad)
         self.edge_key = np.asarray(edge_key, np.int64)
         S = max(len(self.services), 1)
         self.edge_src, self.edge_dst = self.edge_key // S, self.edge_key % S
-        for name in ("svc", "self", "edge", "op"):
+        names = ("svc", "self", "edge", "op")
+        if "crit" in tables:
+            names += ("crit", "critedge")
+            self.n_roots = int(n_roots)
+        for name in names:
             rec, q = tables[name]
             setattr(self, f"{name}_rec", np.asarray(rec, np.int64).reshape(-1, 8))
             setattr(self, f"{name}_q", np.asarray(q, np.uint32).reshape(-1, len(PERMILLE)))
@@ -225,12 +315,35 @@ class TraceStats:
         from .agents.topology import csr_from_edges
         return (list(self.services),) + csr_from_edges(len(self.services), self.edge_src, self.edge_dst)
 
+    @property
+    def has_critical(self):
+        return hasattr(self, "crit_rec")
+
+    def critical_path(self):
+        """Which service the requests were waiting on: one row per service with spans, by critical
+        time descending (ties to the lower id): {service, critical_ms, share, spans_on_path,
+        p95_critical_ms, self_ms, hidden_ms}.  share = the service's critical time / all services';
+        hidden_ms = sum of self time - sum of critical time: the own time that ran beside something
+        slower.  Self time is krca_trace_link's (duration minus ALL children), so the difference is
+        exact for sequential traces only: a span that waited on overlapping children has more
+        critical than self time."""
+        crit, n_on = self.crit_rec[:, R_SUM], self.crit_rec[:, R_N]
+        total = int(crit.sum())
+        rows = sorted((-int(crit[s]), s) for s in range(len(self.services)) if self.svc_rec[s, R_N] > 0)
+        return [{"service": self.services[s], "critical_ms": self._ms(-neg), "share": (-neg / total) if total else 0.0,
+                 "spans_on_path": int(n_on[s]), "p95_critical_ms": self._ms(self.crit_q[s, Q95]),
+                 "self_ms": self._ms(self.self_rec[s, R_SUM]),
+                 "hidden_ms": self._ms(int(self.self_rec[s, R_SUM]) + neg)} for neg, s in rows]
+
     def summary(self):
-        """The additive ``trace_stats`` result key."""
-        return {"spans": self.n_spans, "bad_spans": self.n_bad, "services": len(self.services),
-                "edges": len(self.edge_key), "latency_stats": self.latency_stats(),
-                "error_rate_by_service": self.error_rate_by_service(),
-                "service_dependencies": self.service_dependencies(), "slow_operations": self.slow_operations()}
+        """The additive ``trace_stats`` result key (``critical_path`` only for columns with start_us)."""
+        out = {"spans": self.n_spans, "bad_spans": self.n_bad, "services": len(self.services),
+               "edges": len(self.edge_key), "latency_stats": self.latency_stats(),
+               "error_rate_by_service": self.error_rate_by_service(),
+               "service_dependencies": self.service_dependencies(), "slow_operations": self.slow_operations()}
+        if self.has_critical:
+            out["critical_path"] = self.critical_path()
+        return out
 
 
 def _worst(rows):
@@ -358,4 +471,23 @@ def analyze(st):
                 recommendation="Refactor the service architecture to remove circular dependencies")
         step(f"Detected circular dependency between {', '.join(cn)}",
              "Circular dependencies may lead to deadlocks and complicate scaling")
+    # -- critical path (the reference names the duty, ref:agents/mcp_traces_agent.py:175; no canned text) --
+    if getattr(st, "crit_rec", None) is not None:
+        step(f"Analyzing the critical path of {st.n_roots} requests", "Beginning critical path analysis")
+        crit = st.crit_rec[:, R_SUM].tolist()
+        all_crit = sum(crit)
+        rows = [(crit[s] / all_crit, (s,), s) for s in range(S) if all_crit and crit[s] > CRITICAL_SHARE * all_crit]
+        top, total = _worst(rows)
+        for share, _, s in top:
+            hidden = int(st.self_rec[s, R_SUM]) - crit[s]
+            finding(component=f"Service/{names[s]}", issue="Service dominates the critical path of requests",
+                    severity="medium",
+                    evidence=f"{100 * share:.1f}% of the time requests spent waiting lies in {names[s]}: "
+                             f"{ms(crit[s])} on the critical path over {int(st.crit_rec[s, R_N])} spans, "
+                             f"{ms(hidden)} of its own time hidden behind slower siblings",
+                    recommendation="Optimize this service first: time saved here shortens the requests, "
+                                   "time saved off the critical path does not")
+            step(f"Detected that {names[s]} dominates the critical path", "Requests are waiting on this service")
+        step(f"{total} of {S} services hold more than {100 * CRITICAL_SHARE:.0f}% of the critical path time",
+             f"Reported the {len(top)} largest")
     return out
