@@ -52,7 +52,7 @@ int krca_device_count(int* n_host);
 /* Kernel-development switches and test hooks: KRCA_SCORE_IMPL, KRCA_PPR_GRID, KRCA_PPR_DICT, KRCA_CORR_DEBUG,
  * KRCA_CORR_RS_GRID, KRCA_CORR_BATCH, KRCA_CORR_AMB_TILE, KRCA_PPR_FUSE, KRCA_PPR_NT, KRCA_PPR_XCD, KRCA_LOG_FUSED,
  * KRCA_CORR_RS_GROUP, KRCA_CORR_SIDE, KRCA_CORR_RS_Q16, KRCA_CORR_CAPC, KRCA_CORR_KM_EXTRA, KRCA_CORR_RSG_GRID,
- * KRCA_CORR_PROJ, KRCA_TRACE_IMPL (meanings and defaults: csrc/krca_common.h).  Initialised once from the
+ * KRCA_CORR_PROJ, KRCA_TRACE_IMPL, KRCA_GRAPH_GRID (meanings and defaults: csrc/krca_common.h).  Initialised once from the
  * environment variables of the same names when the library loads; launchers never call getenv.  Process-global,
  * not thread-safe (set them before launching work).  Unknown names: KRCA_EINVAL. */
 int krca_tune_set(const char* name, int32_t value);
@@ -788,6 +788,60 @@ int32_t krca_trace_critical_small_max(void);
 int64_t krca_trace_critical_ws_size(int64_t N);
 int krca_trace_critical(const int32_t* svc, const int32_t* parent, const int64_t* start_us, const uint32_t* dur_us,
                         int64_t N, int32_t S, uint32_t* crit_us, uint8_t* path, void* ws, void* stream);
+
+/* ---- g1: structure of the dependency graph (replaces nx.simple_cycles and the all-pairs
+ * nx.all_simple_paths search of TopologyAgent._analyze_service_dependencies,
+ * ref:agents/topology_agent.py:262-320, and tracecols.first_cycle; csrc/graph_struct.hip).
+ * The graph: row_ptr int64 [N + 1], col int32 [E = row_ptr[N]] and `pull`: 0 = row u lists the
+ * successors of u (krca_betweenness's layout), 1 = row v lists the predecessors of v (krca_ppr's).
+ * Every output is a function of the edge set {u -> v} alone: the same graph in either layout, with its
+ * rows in any order, gives identical bytes.  Duplicate edges and self-loops are legal.  A col entry
+ * outside [0, N) is no edge: it is never used as an index and is counted in n_bad_edges.
+ * 0 <= N <= 2^31 - 2 and pull in {0, 1}, else KRCA_EINVAL before any device work; N == 0 returns the
+ * empty stats without touching a pointer.  The three calls SYNCHRONISE the stream (as krca_trace_edges):
+ * their rounds are plain launches on `stream` driven from the host, which reads a "changed" word back
+ * after each batch; every such loop gives up after N + 2 rounds with KRCA_ENOTCONV.  rounds_host
+ * (nullable) receives the rounds run.  The size functions are host functions without device work.
+ *
+ * krca_graph_scc:  comp[v] = the smallest node id of v's strongly connected component;
+ *   flags[v]: bit 0 = the component is cyclic (two or more nodes, or a self-loop), bit 1 = v has a
+ *   self-loop, bit 2 = v is the representative (comp[v] == v);
+ *   stats_host[6] = {n_components, n_cyclic (components), n_cyclic_nodes, largest_size,
+ *   first_cyclic_label (the smallest; -1: none), n_bad_edges};
+ *   rounds_host[4] = {colouring passes, trim rounds, colouring rounds, reachability rounds}.
+ * krca_graph_chain: comp as krca_graph_scc wrote it.  Over the condensation (one node per component,
+ *   the edges between different components):  depth_dn[v] = components on the longest chain that starts
+ *   at v's component and follows edges forward (1 at a sink), depth_up[v] the same following edges
+ *   backward, next[v] = the label of the forward neighbour component with depth_dn one less (ties: the
+ *   smallest label; -1 at a sink), the same for every node of a component;
+ *   stats_host[2] = {longest = max depth_dn (0 when N = 0), start = the smallest label that attains it
+ *   (-1 when N = 0)}; rounds_host[1].  On an acyclic graph `longest` is the node count of the longest
+ *   simple path; on a cyclic graph it is a LOWER BOUND of it (the longest simple path is NP-hard there).
+ *   A comp that is no component labelling (a label outside [0, N), or labels whose condensation has a
+ *   cycle) never faults: KRCA_EINVAL, outputs unspecified.
+ * krca_graph_cycle: with d(v) = the BFS distance from v to `root` along edges, for the nodes of root's
+ *   component:  hop[v] = the smallest-id successor w of v in the component with d(w) = d(v) - 1 for
+ *   v != root;  hop[root] = the successor w of root in the component with the smallest d(w) (ties: the
+ *   smallest id; root itself when it has a self-loop), -1 when the component is not cyclic;  hop = -1
+ *   outside the component.  root, hop[root], hop[hop[root]], ... back to root is a shortest cycle
+ *   through root.  0 <= root < N; rounds_host[1].
+ * Buffers: comp / flags [N], depth_dn / depth_up / next [N] and hop [N] are fully written, no
+ *   initialisation needed.  ws (krca_graph_scc_ws_size / _chain_ws_size / _cycle_ws_size (N) bytes,
+ *   8-byte aligned) needs none either: each call zeroes the control words it reads back and its
+ *   accumulators, and writes every per-node word (krca_graph_scc: colour and mark, later the label
+ *   minimum and size; krca_graph_chain: the two depths and next per label; krca_graph_cycle: distance
+ *   and hop key) for all N nodes before a round reads it.  Not for graph capture (memsets, read-backs). */
+int64_t krca_graph_scc_ws_size(int64_t N);
+int64_t krca_graph_chain_ws_size(int64_t N);
+int64_t krca_graph_cycle_ws_size(int64_t N);
+int krca_graph_scc(const int64_t* row_ptr, const int32_t* col, int64_t N, int32_t pull, void* ws, int32_t* comp /*[N]*/,
+                   uint8_t* flags /*[N]*/, int64_t* stats_host /*[6]*/, int32_t* rounds_host /*[4], nullable*/,
+                   void* stream);
+int krca_graph_chain(const int64_t* row_ptr, const int32_t* col, int64_t N, int32_t pull, const int32_t* comp, void* ws,
+                     int32_t* depth_dn /*[N]*/, int32_t* depth_up /*[N]*/, int32_t* next /*[N]*/,
+                     int64_t* stats_host /*[2]*/, int32_t* rounds_host /*[1], nullable*/, void* stream);
+int krca_graph_cycle(const int64_t* row_ptr, const int32_t* col, int64_t N, int32_t pull, const int32_t* comp,
+                     int64_t root, void* ws, int32_t* hop /*[N]*/, int32_t* rounds_host /*[1], nullable*/, void* stream);
 
 #ifdef __cplusplus
 }

@@ -45,6 +45,7 @@ const NamedKnob kKnobs[] = {
     {"KRCA_CORR_RSG_GRID", &Tuning::corr_rsg_grid, 0},
     {"KRCA_CORR_PROJ", &Tuning::corr_proj, 2},
     {"KRCA_TRACE_IMPL", &Tuning::trace_impl, 0},
+    {"KRCA_GRAPH_GRID", &Tuning::graph_grid, 0},
 };
 Tuning tuning_from_env() {
   Tuning t{};

@@ -119,6 +119,8 @@ struct Tuning {
                       // 0 never (identical counts)
   int trace_impl;     // KRCA_TRACE_IMPL [0]: krca_trace_stats path: 0 by size, 1 LDS tables per workgroup, 2 global
                       // atomics behind the per-wave fold and the LDS record cache, 3 global atomics, one set per lane; same bits
+  int graph_grid;     // KRCA_GRAPH_GRID [0]: most workgroups per launch of the krca_graph_* kernels (0 = 2^20); waves and
+                      // threads stride over the rows / nodes past it (tests lower it to reach that path at small N)
 };
 const Tuning& tuning();
 int tuning_ppr_dict();

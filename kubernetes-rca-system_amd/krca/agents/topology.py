@@ -8,7 +8,11 @@ quirks are kept: a deployment named like a service merges into that node (``type
 ``deployment``) and its ``selects`` edge becomes a self-loop.
 
 New (additive): :meth:`dependency_csr` exports the graph as the pull-CSR the device PageRank
-kernel consumes.
+kernel consumes.  ``TopologyAgent(..., structure=True)`` replaces the two
+exponential searches of the dependency heuristic (every simple cycle, every simple path of every
+ordered pair) by one ``engine.graph_structure`` call (strongly connected components, a witness
+cycle, the longest chain of the condensation: csrc/graph_struct.hip) and adds the
+key ``topology_structure``; the default keeps the reference's searches to the byte.
 """
 import networkx as nx
 import numpy as np
@@ -24,13 +28,16 @@ def _tmpl_spec(dep):
 
 
 class TopologyAgent(BaseAgent):
-    def __init__(self, k8s_client, engine=None):
+    def __init__(self, k8s_client, engine=None, structure=False):
         super().__init__(k8s_client, engine)
         self.service_graph = nx.DiGraph()
+        self.structure = bool(structure)
+        self._structure = None
 
     def analyze(self, namespace, context=None, **kwargs):
         self.reset()
         self.service_graph = nx.DiGraph()
+        self._structure = None
         try:
             self._maybe_set_context(context)
             c = self.k8s_client
@@ -53,6 +60,8 @@ class TopologyAgent(BaseAgent):
             self._analyze_resource_dependencies(deployments, configmaps, secrets)
             res = self.get_results()
             res['topology_data'] = self._prepare_topology_data()
+            if self._structure is not None:
+                res['topology_structure'] = self._structure.summary()  # additive key
             return res
         except Exception as e:
             return self._error_result("topology", e)
@@ -181,6 +190,8 @@ class TopologyAgent(BaseAgent):
 
     # -- heuristics (ref :262-401) -------------------------------------------------------
     def _analyze_service_dependencies(self):
+        if self.structure:
+            return self._analyze_structure()
         g = self.service_graph
         try:
             cycles = list(nx.simple_cycles(g))
@@ -217,6 +228,52 @@ class TopologyAgent(BaseAgent):
             self.add_reasoning_step(observation=f"Detected a dependency chain of length {len(best)}: {chain}",
                                     conclusion="Long dependency chains can increase latency and reduce reliability")
 
+    def _out_csr(self, g):
+        """Out-edge CSR of g: node order = g's insertion order, out-edges in adjacency order."""
+        nodes = list(g.nodes)
+        pos = {n: i for i, n in enumerate(nodes)}
+        row_ptr = [0]
+        col = []
+        nbrs = g.successors if g.is_directed() else g.neighbors
+        for n in nodes:
+            col.extend(pos[m] for m in nbrs(n))
+            row_ptr.append(len(col))
+        return nodes, row_ptr, col
+
+    def _analyze_structure(self):
+        """The dependency heuristic from one engine.graph_structure call: the circular-dependency
+        finding shows the device's witness cycle and the step counts cyclic groups and their nodes
+        (not simple cycles: their number is what does not scale); the long-chain finding is raised
+        iff the longest chain of the condensation has >= 4 components -- on an acyclic graph exactly
+        the reference's longest simple path, on a cyclic graph a lower bound of it."""
+        nodes, row_ptr, col = self._out_csr(self.service_graph)
+        gs = self.engine.graph_structure(np.asarray(row_ptr, np.int64), np.asarray(col, np.int32), pull=False)
+        self._structure = gs
+        cyc = gs.first_cycle()
+        if cyc:
+            names = [nodes[i] for i in cyc]
+            self.add_finding(component="Service Architecture",
+                             issue="Circular dependency detected in service architecture", severity="medium",
+                             evidence=f"Dependency cycle: {' → '.join(names + [names[0]])}",
+                             recommendation="Refactor the service architecture to eliminate circular dependencies")
+            self.add_reasoning_step(
+                observation=f"Detected {gs.n_cyclic} circular dependency groups holding {gs.n_cyclic_nodes} nodes "
+                            f"in the service graph",
+                conclusion="Circular dependencies can lead to deployment and scaling issues")
+        if gs.longest is not None and gs.longest >= 4:
+            parts = []
+            for label in gs.longest_chain():
+                if gs.flags[label] & 1:  # a cyclic group stands in the chain as its members
+                    parts.append("{" + ", ".join(nodes[i] for i in gs.members(label)) + "}")
+                else:
+                    parts.append(nodes[label])
+            chain = ' → '.join(parts)
+            self.add_finding(component="Service Architecture", issue="Long dependency chain detected", severity="low",
+                             evidence=f"Long dependency path: {chain}",
+                             recommendation="Consider simplifying the architecture or implementing caching to reduce dependency chain impacts")
+            self.add_reasoning_step(observation=f"Detected a dependency chain of length {gs.longest}: {chain}",
+                                    conclusion="Long dependency chains can increase latency and reduce reliability")
+
     def _analyze_single_points_of_failure(self):
         g = self.service_graph
         try:
@@ -240,14 +297,7 @@ class TopologyAgent(BaseAgent):
     def _betweenness(self, g):
         """nx.betweenness_centrality(g) (ref :329) on the device (krca_betweenness):
         node order = g's insertion order, out-edges in adjacency order; {node: value}."""
-        nodes = list(g.nodes)
-        pos = {n: i for i, n in enumerate(nodes)}
-        row_ptr = [0]
-        col = []
-        nbrs = g.successors if g.is_directed() else g.neighbors
-        for n in nodes:
-            col.extend(pos[m] for m in nbrs(n))
-            row_ptr.append(len(col))
+        nodes, row_ptr, col = self._out_csr(g)
         bc = self.engine.betweenness(row_ptr, col, normalized=True, directed=g.is_directed())
         return {n: float(bc[i]) for i, n in enumerate(nodes)}
 

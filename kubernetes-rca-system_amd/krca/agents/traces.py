@@ -6,7 +6,8 @@ findings are canned, :209-381); kept so the comprehensive run correlates identic
 A client that serves spans (``get_span_columns(namespace)`` -> krca.tracecols.SpanColumns, or
 ``get_trace_details`` spans with ``parentId``) takes the data path instead: the same analyses in the
 same order, computed on the device by ``engine.trace_analyze`` (krca/tracecols.py), plus the additive
-``trace_stats`` key.
+``trace_stats`` key.  ``TracesAgent(..., structure=True)`` takes the call graph's circular dependency
+from ``engine.graph_structure`` (csrc/graph_struct.hip) instead of the host's networkx search.
 """
 from .. import tracecols
 from .base import BaseAgent
@@ -15,6 +16,10 @@ _TRACE_KEYS = ('jaeger', 'zipkin', 'tracing', 'otel', 'opentelemetry')
 
 
 class TracesAgent(BaseAgent):
+    def __init__(self, k8s_client, engine=None, structure=False):
+        super().__init__(k8s_client, engine)
+        self.structure = bool(structure)
+
     def analyze(self, namespace, context=None, **kwargs):
         self.reset()
         try:
@@ -76,7 +81,12 @@ class TracesAgent(BaseAgent):
         if len(cols) == 0:
             return self.get_results()
         stats = self.engine.trace_analyze(cols)
-        for kind, kw in tracecols.analyze(stats):
+        cycle = None
+        if self.structure:  # the device's witness cycle of the call graph, or False: acyclic
+            from ..graphstruct import out_csr, rotate_to_lowest
+            rp, col = out_csr(len(stats.services), stats.edge_src, stats.edge_dst)
+            cycle = rotate_to_lowest(self.engine.graph_structure(rp, col, pull=False, chain=False).first_cycle()) or False
+        for kind, kw in tracecols.analyze(stats, cycle=cycle):
             (self.add_finding if kind == 'finding' else self.add_reasoning_step)(**kw)
         res = self.get_results()
         res["trace_stats"] = stats.summary()  # additive key

@@ -140,6 +140,12 @@ SIGNATURES = {
     "krca_trace_critical_small_max": (c_i32, []),
     "krca_trace_critical_ws_size": (c_i64, [c_i64]),
     "krca_trace_critical": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    "krca_graph_scc_ws_size": (c_i64, [c_i64]),
+    "krca_graph_chain_ws_size": (c_i64, [c_i64]),
+    "krca_graph_cycle_ws_size": (c_i64, [c_i64]),
+    "krca_graph_scc": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "krca_graph_chain": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "krca_graph_cycle": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
 }
 
 KRCA_ENOTCONV = -70
@@ -504,6 +510,68 @@ class NativeEngine:
         _check(self.lib.krca_betweenness(self.ptr(rp_d), self.ptr(col_d), N, int(bool(normalized)), int(bool(directed)),
                                          batch, self.ptr(ws), self.ptr(bc), self._stream()), "krca_betweenness")
         return bc[:N].cpu().numpy()
+
+    # -- g1 graph structure: components, longest chain, witness cycle (csrc/graph_struct.hip) ------
+    # the three *_device calls take device tensors (row_ptr int64 [N + 1], col int32, at least one
+    # element each) and SYNCHRONISE the stream: their rounds are driven from the host
+    def graph_scc_device(self, rp, cl, N, pull):
+        """-> (comp int32, flags uint8 device tensors of max(N, 1), stats [6], rounds [4] host ints)."""
+        torch = self.torch
+        comp = torch.empty(max(N, 1), dtype=torch.int32, device=self.device)
+        flags = torch.empty(max(N, 1), dtype=torch.uint8, device=self.device)
+        stats, rounds = (c_i64 * 6)(), (c_i32 * 4)()
+        ws = self._workspace("graph_scc", self.lib.krca_graph_scc_ws_size(N))
+        _check(self.lib.krca_graph_scc(self.ptr(rp), self.ptr(cl), N, int(pull), self.ptr(ws), self.ptr(comp),
+                                       self.ptr(flags), stats, rounds, self._stream()), "krca_graph_scc")
+        return comp, flags, [int(x) for x in stats], [int(x) for x in rounds]
+
+    def graph_chain_device(self, rp, cl, N, pull, comp):
+        """-> (depth_dn, depth_up, next int32 device tensors, stats [2], rounds)."""
+        torch = self.torch
+        dn, up, nx = (torch.empty(max(N, 1), dtype=torch.int32, device=self.device) for _ in range(3))
+        stats, rounds = (c_i64 * 2)(), (c_i32 * 1)()
+        ws = self._workspace("graph_chain", self.lib.krca_graph_chain_ws_size(N))
+        _check(self.lib.krca_graph_chain(self.ptr(rp), self.ptr(cl), N, int(pull), self.ptr(comp), self.ptr(ws),
+                                         self.ptr(dn), self.ptr(up), self.ptr(nx), stats, rounds, self._stream()),
+               "krca_graph_chain")
+        return dn, up, nx, [int(x) for x in stats], int(rounds[0])
+
+    def graph_cycle_device(self, rp, cl, N, pull, comp, root):
+        """-> (hop int32 device tensor, rounds)."""
+        hop = self.torch.empty(max(N, 1), dtype=self.torch.int32, device=self.device)
+        rounds = (c_i32 * 1)()
+        ws = self._workspace("graph_cycle", self.lib.krca_graph_cycle_ws_size(N))
+        _check(self.lib.krca_graph_cycle(self.ptr(rp), self.ptr(cl), N, int(pull), self.ptr(comp), int(root),
+                                         self.ptr(ws), self.ptr(hop), rounds, self._stream()), "krca_graph_cycle")
+        return hop, int(rounds[0])
+
+    def graph_structure(self, row_ptr, col, pull=False, chain=True, cycle=True):
+        """CSR (host or device arrays; pull=False: row u = successors of u, pull=True: row v =
+        predecessors of v) -> krca.graphstruct.GraphStructure (host arrays).  chain: also the depths
+        and `next` of the condensation; cycle: also the witness cycle through the first cyclic
+        component's label, when there is one."""
+        from .graphstruct import GraphStructure
+        torch = self.torch
+        N = int(len(row_ptr)) - 1
+        if N < 0:
+            raise KrcaError("graph_structure: row_ptr must have N + 1 entries")
+        rp, cl = self._dev_n(row_ptr, np.int64), self._dev_n(col, np.int32)
+        if rp.dtype != torch.int64 or cl.dtype != torch.int32:
+            raise KrcaError("graph_structure: row_ptr must be int64 and col int32")
+        pull = int(bool(pull))
+        comp, flags, stats, rounds = self.graph_scc_device(rp, cl, N, pull)
+        gs = GraphStructure(N, comp[:N].cpu().numpy(), flags[:N].cpu().numpy(), *stats)
+        gs.rounds = dict(zip(("passes", "trim", "colour", "reach"), rounds))
+        if chain:
+            dn, up, nx, cstats, gs.rounds["chain"] = self.graph_chain_device(rp, cl, N, pull, comp)
+            gs.depth_dn, gs.depth_up, gs.next = (t[:N].cpu().numpy() for t in (dn, up, nx))
+            gs.longest, gs.start = cstats
+        if cycle and gs.first_cyclic_label >= 0:
+            hop, gs.rounds["cycle"] = self.graph_cycle_device(rp, cl, N, pull, comp, gs.first_cyclic_label)
+            gs.root, gs.hop = gs.first_cyclic_label, hop[:N].cpu().numpy()
+        elif cycle:
+            gs.hop = np.full(N, -1, np.int32)
+        return gs
 
     # -- f2 service-graph construction --------------------------------------------------------
     def selector_match(self, lab, lab_off, sel, sel_off):

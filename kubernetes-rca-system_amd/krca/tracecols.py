@@ -368,10 +368,13 @@ def first_cycle(n, src, dst):
     return cyc
 
 
-def analyze(st):
+def analyze(st, cycle=None):
     """TraceStats -> findings and reasoning steps in the reference's order of analyses
     (ref:agents/traces_agent.py:209-381: latency, errors, dependencies), with its component / issue /
-    recommendation strings and measured values in the evidence: a list of ('finding' | 'step', kwargs)."""
+    recommendation strings and measured values in the evidence: a list of ('finding' | 'step', kwargs).
+    cycle: None -> first_cycle (networkx, host) finds the call graph's circular dependency; a list of
+    service ids -> that cycle is reported and first_cycle is not called; False -> the caller found the
+    graph acyclic (NativeEngine.graph_structure), first_cycle is not called either."""
     out = []
     names = st.services
     S = len(names)
@@ -463,7 +466,7 @@ def analyze(st):
         step(f"Detected high dependency of {a} on {b}",
              "Service coupling may lead to reliability issues if the dependency fails")
     step(f"{total} call edges carry more than half of their caller's outgoing calls", f"Reported the {len(top)} largest")
-    cyc = first_cycle(S, src, dst)
+    cyc = first_cycle(S, src, dst) if cycle is None else cycle
     if cyc:
         cn = [names[i] for i in cyc]
         finding(component=f"Services/{'↔'.join(cn)}", issue="Circular dependency detected between services",
