@@ -208,17 +208,32 @@ int krca_log_scan(const uint8_t* text, int64_t nbytes, const int64_t* doc_off, i
  * same line_mask layout (bits 0..ncat-1 the categories, bits 16..16+ncat-1 the example marks), with
  * hist [D][ncat] and examples [D][ncat][3] strided by the tables' ncat.
  *
- * Pattern subset: every regex expands to a finite set of fixed-length alternatives of
- * single-code-point atoms (literals, '.', \d \D \w \W \s \S, bracket classes; {n}, {m,n}, ? on one
- * atom).  No unbounded quantifier: the wave-per-line kernel for lines over 1 KiB starts each of its
- * 64 segments from the start state after a warm-up of `warm` code points (the longest alternative
- * minus one), which is exact only when no match is longer than warm + 1 code points.
+ * Pattern subset: every regex expands to a finite set of alternatives of single-code-point atoms
+ * (literals, '.', \d \D \w \W \s \S, bracket classes; {n}, {m,n}, ? on one atom), fixed-length by
+ * default.  compile_patterns(..., unbounded=True) also takes * + {m,} {,} on one atom (x{m,} is m
+ * copies of x and a loop item on x); quantifiers on a group, lazy / possessive forms, anchors, \b,
+ * nested groups, back-references, look-around, inline flags and alternatives that can match the
+ * empty string stay refused.  The tables are one product DFA: a \d+-style loop is nearly free, each
+ * ".*" between literals roughly doubles the states (one fits beside the 13 shipped patterns, two
+ * pass KRCA_LOG_MAX_NSTATE).
+ *
+ * Long lines (over 1 KiB) take a wave per line, 64 segments.  log_dfa_long_rt starts each segment
+ * from the start state after a warm-up of `warm` code points (the longest alternative minus one):
+ * exact only when no match is longer than warm + 1 code points, i.e. for fixed-length sets.  Tables
+ * with KRCA_LOG_FLAG_CARRY (bit 0 of the header's flag word; the compiler sets it for a set with
+ * loop items) take log_dfa_long_carry_rt instead: after the same speculative pass each lane compares
+ * its entry state with its predecessor's exit state, and the lanes that differ re-walk their
+ * segment from it, until a wave-wide vote finds no difference.  After round r lanes 0..r are final,
+ * so at most 63 rounds and the result is exact for every DFA; `warm` (loops at their minimum, at
+ * most 63) is only the speculation's warm-up.  Worst case (a state that survives every boundary,
+ * "error.*" seen in the first segment): one serial walk of the line.  No workspace, no atomics; the
+ * walk of lines up to 1 KiB (a lane per line from its first byte) is the same for both.
  *
  * Table image (host memory, little-endian, version 1):
  *   offset  0  uint32 magic = KRCA_LOG_IMAGE_MAGIC, version = KRCA_LOG_IMAGE_VERSION,
  *              ncat, nsym, nstate, nrange, warm, other   (eight uint32)
  *          32  uint64 digest (patterns.pattern_digest of the (name, regex) pairs)
- *          40  uint32 nbytes (the whole image), uint32 0
+ *          40  uint32 nbytes (the whole image), uint32 flags (KRCA_LOG_FLAG_CARRY or 0)
  *          48  uint8  ascii_sym[128]        symbol of each ASCII code point, KRCA_LOG_SYM_SEP for a separator
  *         176  uint32 ranges[nrange][3]     {lo, hi, symbol}: non-ASCII code points, every other one -> `other`
  *              uint16 trans[nstate * nsym]  target state of (state, symbol); state 0 is the start state
@@ -228,8 +243,8 @@ int krca_log_scan(const uint8_t* text, int64_t nbytes, const int64_t* doc_off, i
  *
  * krca_log_tables_check (host only, no GPU needed): validates an image -- magic, version, sizes, the
  *   limits, every transition < nstate, every mask < 1 << ncat, ranges sorted, disjoint, lo <= hi, above
- *   0x7F and below 0x110000, every symbol < nsym (or KRCA_LOG_SYM_SEP) and other < nsym -- and fills
- *   *dims (nullable).  KRCA_EINVAL with krca_last_error() naming the field otherwise.
+ *   0x7F and below 0x110000, every symbol < nsym (or KRCA_LOG_SYM_SEP), other < nsym and no flag bit
+ *   but KRCA_LOG_FLAG_CARRY -- and fills *dims (nullable; dims->flags reports the flag word).  KRCA_EINVAL with krca_last_error() naming the field otherwise.
  * krca_log_tables_dev_size (host only): bytes of the device form for these dimensions (0 when they
  *   break a limit).  The device form is the walk kernels' LDS layout, copied as it is: 16-bit entries
  *   (target state | 0x8000 when the target reports a category; category masks are read from out[]
@@ -262,9 +277,11 @@ int krca_log_scan(const uint8_t* text, int64_t nbytes, const int64_t* doc_off, i
 #define KRCA_LOG_MAX_NSTATE 1024
 #define KRCA_LOG_MAX_NRANGE 1024
 #define KRCA_LOG_MAX_WARM 63
+#define KRCA_LOG_FLAG_CARRY 1u /* long lines: carry the state from segment to segment */
 typedef struct krca_log_dims {
   int32_t ncat, nsym, nstate, nrange, warm, other;
   uint64_t digest;
+  uint32_t flags; /* the image's flag word (trailing: the fields above keep their offsets) */
 } krca_log_dims;
 int krca_log_tables_check(const void* image_host, int64_t image_bytes, krca_log_dims* dims_host /*nullable*/);
 int64_t krca_log_tables_dev_size(const krca_log_dims* dims_host);

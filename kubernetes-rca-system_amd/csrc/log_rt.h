@@ -247,6 +247,90 @@ __global__ __launch_bounds__(TPB) void log_dfa_long_rt(const uint8_t* __restrict
   }
 }
 
+// ---- log_dfa_long_carry_rt: log_dfa_long_rt for tables with KRCA_LOG_FLAG_CARRY (loop items: a match has
+// no longest length, so no warm-up makes a segment's start state right).  Same segments, same warm-up
+// and first walk; then the state is carried along the wave.  Per round: prev = the predecessor lane's
+// exit state (the start state for lane 0); a wave-wide vote -- executed by all 64 lanes, those with an
+// empty segment included -- ends the line when no lane has prev != entry; else the lanes that differ
+// take prev as their entry and walk their segment again.  After round r lanes 0..r hold the true
+// states, so the loop ends within 63 rounds for every table (the bound is also its trip count).
+// Masks of superseded walks stay ORed in: every walk starts from the state that some suffix of the
+// text before its segment leads to from the start state, so what it reports is a match inside the
+// line, and the last walk of every lane is the true one.  An empty segment hands its entry on.
+// Worst case: a state that survives every boundary (".*" armed in segment 0) makes lane r walk in round
+// r alone -- one serial walk of the line.  No workspace, no atomics; reads the bytes the first walk reads.
+template <int RSL>
+__global__ __launch_bounds__(TPB) void log_dfa_long_carry_rt(const uint8_t* __restrict__ text, int64_t nbytes,
+                                                             const int64_t* __restrict__ line_start,
+                                                             const int64_t* __restrict__ line_end,
+                                                             uint32_t* __restrict__ line_mask,
+                                                             const int32_t* __restrict__ long_q,
+                                                             const int32_t* __restrict__ n_long,
+                                                             const uint8_t* __restrict__ tab, const RtDims dm) {
+  const int nq = *n_long;
+  if ((int64_t)blockIdx.x * (TPB / 64) >= nq) return;  // no long line for this block: skip the table fill
+  rt_fill<RSL>(tab, dm);
+  const RtTab T(dm);
+  const int lane = threadIdx.x & 63;
+  Bytes B;
+  B.init(text, nbytes);
+  auto symbol = [&](uint32_t cp) -> uint32_t {
+    return cp < 128 ? (uint32_t)T.sym[cp] >> 1 : rt_cp_sym(T.rng, dm.nrange, (uint32_t)dm.other, cp);
+  };
+  auto entry = [&](uint32_t st, uint32_t sy) -> uint32_t {
+    return *reinterpret_cast<const uint16_t*>(T.trans + ((((st & kRtState) << RSL) + sy) << 1));
+  };
+  // (j is the same for the 64 lanes of a wave: the shuffles and the vote below run with every lane active)
+  for (int j = (int)(blockIdx.x * (TPB / 64) + (threadIdx.x >> 6)); j < nq; j += (int)(gridDim.x * (TPB / 64))) {
+    const int64_t l = long_q[j];
+    const int64_t s = line_start[l], e = line_end[l];
+    const int64_t seg = (e - s + 63) / 64;
+    const int64_t a = min(e, s + lane * seg), b = min(e, a + seg);
+    uint32_t mask = 0;
+    const int64_t p0 = a > s ? cp_align(B, a, e) : s;  // first code point starting in [a, b)
+    uint32_t st_in = 0;
+    if (p0 > s && p0 < b) {  // warm-up over the <= warm code points of the line before p0 (speculation only)
+      int64_t k = p0;
+      int seen = 0;
+      while (k > s && seen < dm.warm) {
+        const uint32_t c = B.at(k - 1);
+        --k;
+        if ((c & 0xC0) != 0x80) ++seen;
+      }
+      while (k < p0) {
+        uint32_t cp;
+        const int len = decode(B, k, cp);
+        st_in = entry(st_in, symbol(cp));
+        k += len;
+      }
+      st_in &= kRtState;
+    }
+    uint32_t st_out = 0;
+    bool redo = true;  // round 0: every lane's first walk
+    for (int round = 0;; ++round) {
+      if (redo) {  // [p0, b) from st_in (an empty segment hands it on)
+        uint32_t st = st_in;
+        for (int64_t p = p0; p < b;) {
+          uint32_t cp;
+          const int len = decode(B, p, cp);
+          st = entry(st, symbol(cp));
+          if (__builtin_expect((st & kRtAcc) != 0, 0)) mask |= T.out[st & kRtState];
+          p += len;
+        }
+        st_out = st & kRtState;
+      }
+      if (round == 63) break;
+      uint32_t prev = __shfl_up(st_out, 1, 64);
+      if (lane == 0) prev = 0;
+      redo = prev != st_in;
+      if (!__any(redo)) break;
+      if (redo) st_in = prev;
+    }
+    for (int off = 32; off > 0; off >>= 1) mask |= __shfl_xor(mask, off, 64);
+    if (lane == 0) line_mask[l] = mask;
+  }
+}
+
 // ---- log_hist_rt: log_hist with the category count as an argument (output stride and loop bounds);
 // the per-lane arrays stay sized for KRCA_LOG_MAX_NCAT
 constexpr int RT_NC = KRCA_LOG_MAX_NCAT;
@@ -374,7 +458,7 @@ __global__ __launch_bounds__(TPB) void log_hist_rt(const int64_t* __restrict__ d
   for (int i = threadIdx.x; i < nv * ncat; i += TPB) hist[d0 * ncat + i] = s_ex[(i / ncat) * RT_NC + i % ncat];
 }
 
-// ---- launch: LDS the runtime grants, occupancy, the three kernels ------------------------------------
+// ---- launch: LDS the runtime grants, occupancy, the walk, one of the two long-line kernels, the histogram ----
 inline RtDims rt_dims(const krca_log_dims& d, const krca::LogRtLayout& l) {
   RtDims r;
   r.ncat = d.ncat, r.nsym = d.nsym, r.nstate = d.nstate, r.nrange = d.nrange, r.warm = d.warm, r.other = d.other;
@@ -420,6 +504,7 @@ inline int rt_prepare(const void* kernel, const char* name, int tpb, uint32_t ld
 struct RtPlan {  // what krca_log_scan_tables / krca_log_match_tables launch, decided before the first kernel
   RtDims dm;
   int rsl;
+  bool carry;  // KRCA_LOG_FLAG_CARRY: long lines go to log_dfa_long_carry_rt
   int64_t walk_resident, long_resident;
 };
 
@@ -427,20 +512,23 @@ template <int RSL>
 int rt_plan_t(RtPlan& p, hipStream_t st) {
   // the runtime's answers for the last (device, table size) of this thread: a scan per window asks once, not
   // five host queries in front of every scan's first launch
-  static thread_local struct { int dev; uint32_t bytes; int64_t walk, lng; } last = {-1, 0, 0, 0};
+  static thread_local struct { int dev; uint32_t bytes; bool carry; int64_t walk, lng; } last = {-1, 0, false, 0, 0};
   int dev = 0;
   KRCA_HIP(st ? hipStreamGetDevice(st, &dev) : hipGetDevice(&dev));
-  if (last.dev == dev && last.bytes == p.dm.bytes) {
+  if (last.dev == dev && last.bytes == p.dm.bytes && last.carry == p.carry) {
     p.walk_resident = last.walk, p.long_resident = last.lng;
     return KRCA_OK;
   }
-  static std::atomic<uint32_t> asked_walk{0}, asked_long{0};  // largest opt-in requested per kernel
+  static std::atomic<uint32_t> asked_walk{0}, asked_long{0}, asked_carry{0};  // largest opt-in requested per kernel
   int rc = rt_prepare(reinterpret_cast<const void*>(&log_dfa_rt<RSL>), "log_dfa_rt", DFA_TPB, p.dm.bytes, st, &p.walk_resident,
                       asked_walk);
-  if (!rc)
+  if (!rc && !p.carry)
     rc = rt_prepare(reinterpret_cast<const void*>(&log_dfa_long_rt<RSL>), "log_dfa_long_rt", TPB, p.dm.bytes, st,
                     &p.long_resident, asked_long);
-  if (!rc) last = {dev, p.dm.bytes, p.walk_resident, p.long_resident};
+  if (!rc && p.carry)
+    rc = rt_prepare(reinterpret_cast<const void*>(&log_dfa_long_carry_rt<RSL>), "log_dfa_long_carry_rt", TPB, p.dm.bytes, st,
+                    &p.long_resident, asked_carry);
+  if (!rc) last = {dev, p.dm.bytes, p.carry, p.walk_resident, p.long_resident};
   return rc;
 }
 
@@ -454,6 +542,7 @@ inline int rt_plan(const char* who, const void* tables_dev, int64_t tables_dev_b
   KRCA_CHECK_ARG(((uintptr_t)tables_dev & 3) == 0, "%s: device tables must be 4-byte aligned", who);
   p.dm = rt_dims(*dims, l);
   p.rsl = l.rsl;
+  p.carry = (dims->flags & KRCA_LOG_FLAG_CARRY) != 0;
   return l.rsl == 5 ? rt_plan_t<5>(p, st) : rt_plan_t<6>(p, st);
 }
 
@@ -466,6 +555,7 @@ void rt_launch_walk(const RtPlan& p, hipStream_t st, const uint8_t* text, int64_
   hipLaunchKernelGGL(log_dfa_rt<RSL>, dim3((unsigned)grid), dim3(DFA_TPB), p.dm.bytes, st, text, nbytes, L, Ld, cap,
                      line_start, line_end, line_mask, long_q, n_long, tab, p.dm);
   const int64_t grid_long = std::max<int64_t>(1, std::min<int64_t>(256, p.long_resident));
-  hipLaunchKernelGGL(log_dfa_long_rt<RSL>, dim3((unsigned)grid_long), dim3(TPB), p.dm.bytes, st, text, nbytes, line_start,
-                     line_end, line_mask, (const int32_t*)long_q, (const int32_t*)n_long, tab, p.dm);
+  hipLaunchKernelGGL(p.carry ? log_dfa_long_carry_rt<RSL> : log_dfa_long_rt<RSL>, dim3((unsigned)grid_long), dim3(TPB),
+                     p.dm.bytes, st, text, nbytes, line_start, line_end, line_mask, (const int32_t*)long_q,
+                     (const int32_t*)n_long, tab, p.dm);
 }

@@ -1,5 +1,5 @@
 // Device form of run-time log pattern tables (include/krca.h, "pattern tables compiled at run
-// time"): the LDS layout of log_dfa_rt / log_dfa_long_rt, shared by the host packer
+// time"): the LDS layout of log_dfa_rt / log_dfa_long_rt / log_dfa_long_carry_rt, shared by the host packer
 // (log_tables.cpp) and the kernels (log_rt.h).  All offsets in bytes, multiples of 16.
 #pragma once
 #include <stdint.h>
@@ -24,7 +24,7 @@ struct LogRtLayout {
 inline bool log_dims_ok(const krca_log_dims& d) {
   return d.ncat >= 1 && d.ncat <= KRCA_LOG_MAX_NCAT && d.nsym >= 1 && d.nsym <= KRCA_LOG_MAX_NSYM && d.nstate >= 1 &&
          d.nstate <= KRCA_LOG_MAX_NSTATE && d.nrange >= 0 && d.nrange <= KRCA_LOG_MAX_NRANGE && d.warm >= 0 &&
-         d.warm <= KRCA_LOG_MAX_WARM && d.other >= 0 && d.other < d.nsym;
+         d.warm <= KRCA_LOG_MAX_WARM && d.other >= 0 && d.other < d.nsym && (d.flags & ~KRCA_LOG_FLAG_CARRY) == 0;
 }
 
 inline LogRtLayout log_rt_layout(const krca_log_dims& d) {

@@ -84,8 +84,11 @@ int krca_log_tables_check(const void* image_host, int64_t image_bytes, krca_log_
   d.digest = (uint64_t)rd32(im + 32) | (uint64_t)rd32(im + 36) << 32;
   int64_t need = kHeader + kAscii + (int64_t)d.nrange * 12 + (int64_t)d.nstate * d.nsym * 2 + (int64_t)d.nstate * 2;
   need = (need + 7) & ~(int64_t)7;
-  KRCA_CHECK_ARG(rd32(im + 40) == need && rd32(im + 44) == 0,
-                 "krca_log_tables_check: header says %u bytes, its dimensions need %lld", rd32(im + 40), (long long)need);
+  KRCA_CHECK_ARG(rd32(im + 40) == need, "krca_log_tables_check: header says %u bytes, its dimensions need %lld",
+                 rd32(im + 40), (long long)need);
+  d.flags = rd32(im + 44);
+  KRCA_CHECK_ARG((d.flags & ~KRCA_LOG_FLAG_CARRY) == 0, "krca_log_tables_check: flags 0x%X has a bit this library does not know",
+                 d.flags);
   KRCA_CHECK_ARG(image_bytes >= need, "krca_log_tables_check: truncated image: %lld bytes of %lld", (long long)image_bytes,
                  (long long)need);
   const ImageView v = view(im, d);

@@ -36,14 +36,19 @@ def format_examples(lines, n):
 
 
 class LogsAgent(BaseAgent):
-    def __init__(self, k8s_client, engine=None, compile_patterns=False):
+    def __init__(self, k8s_client, engine=None, compile_patterns=False, unbounded=False):
         """compile_patterns: opt in to matching an EDITED ``error_patterns`` dict, as the reference does
         (:20, :147-149): at analyze() time the dict's (name, regex) pairs are compiled into device tables
         (krca/logdfa.py: fixed-length alternatives only; anything else gives the agent's error result).
-        Default False: an edited dict is refused, as before."""
+        Default False: an edited dict is refused, as before.
+        unbounded: with compile_patterns, also take ``* + {m,}`` on one atom (``\\d+``, ``Exception.*at``;
+        krca/logdfa.py says what fits).  Default False: those give the error result, as before."""
         super().__init__(k8s_client, engine)
+        if unbounded and not compile_patterns:
+            raise ValueError("LogsAgent: unbounded=True needs compile_patterns=True")
         self.error_patterns = dict(P.ERROR_PATTERNS)  # public attribute of the reference (:20)
         self.compile_patterns = bool(compile_patterns)
+        self.unbounded = bool(unbounded)
 
     def _runtime_tables(self):
         """Device tables for an edited error_patterns under compile_patterns=True; None for the shipped
@@ -51,7 +56,9 @@ class LogsAgent(BaseAgent):
         pats = list(self.error_patterns.items())
         if not self.compile_patterns or pats == list(P.ERROR_PATTERNS):
             return None
-        return self.engine.log_tables(pats)  # cached by digest; PatternsUnsupported -> the error result
+        # cached by digest; PatternsUnsupported -> the error result.  The keyword goes only when set:
+        # engines with the one-argument log_tables keep working
+        return self.engine.log_tables(pats, unbounded=True) if self.unbounded else self.engine.log_tables(pats)
 
     def _check_patterns_compiled(self):
         """The device matcher is compiled from krca/patterns.py (csrc/gen_log_dfa.py); the reference

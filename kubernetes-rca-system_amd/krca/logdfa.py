@@ -11,17 +11,31 @@ Semantics are the reference's (ref:agents/logs_agent.py:147-149): line ``l`` of
 points are grouped into symbols by asking CPython's own ``re`` which atoms match them, so the
 tables are exact for the running interpreter's Unicode data.
 
-Supported syntax: every regex must expand to a finite set of fixed-length alternatives of
-single-code-point atoms -- top-level ``|`` (optionally inside ONE outer pair of parentheses);
-atoms: a literal, ``.``, ``\\d \\D \\w \\W \\s \\S``, an escaped metacharacter, a bracket class with
-ranges and negation; quantifiers ``{n}``, ``{m,n}`` and ``?`` on one atom (expanded into
-alternatives).  Everything else raises :class:`PatternsUnsupported`: ``* + {m,}``, anchors,
-``\\b``, nested groups, back-references, look-around, inline flags, a regex ``re.compile`` rejects.
+Supported syntax: every regex must expand to a finite set of alternatives of single-code-point
+atoms -- top-level ``|`` (optionally inside ONE outer pair of parentheses); atoms: a literal,
+``.``, ``\\d \\D \\w \\W \\s \\S``, an escaped metacharacter, a bracket class with ranges and
+negation; quantifiers ``{n}``, ``{m,n}`` and ``?`` on one atom (expanded into alternatives).
+By default the alternatives are fixed-length and everything else raises
+:class:`PatternsUnsupported`: ``* + {m,}``, anchors, ``\\b``, nested groups, back-references,
+look-around, inline flags, a regex ``re.compile`` rejects.
 
-Why fixed length: the device's wave-per-line kernel starts each segment of a long line from the
-start state after a warm-up of ``warm`` code points (the longest alternative minus one); that is
-exact only when no match is longer than ``warm + 1`` code points.  Unbounded quantifiers are out
-of scope.
+``compile_patterns(patterns, unbounded=True)`` also takes ``*``, ``+``, ``{m,}`` and ``{,}`` on one
+atom: ``x{m,}`` is m copies of ``x`` followed by a LOOP ITEM on ``x``, a position of the alternative
+that a matching code point does not leave.  Still refused: a quantifier on anything but one atom,
+the lazy and possessive forms, and an alternative that can match the empty string (``a*``,
+``x*y?``: it matches every line).  What loops cost is states, not symbols: a ``\\d+``-style loop
+whose atom the next atom excludes is nearly free, but ``.*`` between two literals keeps "the
+first literal was seen" alive beside every position of every other pattern and roughly doubles
+the product DFA.  One ``.*`` fits beside the 13 shipped patterns (737 states of 1024), two do
+not; the "states" limit then raises with the measured count.
+
+Long lines: the device's wave-per-line kernel starts each of its 64 segments from the start state
+after a warm-up of ``warm`` code points.  For a fixed-length set ``warm`` is the longest
+alternative minus one and that is exact.  A set with loop items has no such bound: its image
+carries ``FLAG_CARRY`` and the launcher takes ``log_dfa_long_carry_rt``, which hands each segment's
+exit state to the next lane and re-walks until nothing changes; ``warm`` (loops counted at their
+minimum, at most 63) is then only the speculation's warm-up.  :func:`simulate_segments` restates
+that kernel in Python.
 """
 import re
 import struct
@@ -45,7 +59,8 @@ MAX_ALTS = 256     # alternatives in the set after expansion
 
 IMAGE_MAGIC = 0x544C524B  # "KRLT"
 IMAGE_VERSION = 1
-IMAGE_HEADER = struct.Struct("<8IQ2I")  # magic version ncat nsym nstate nrange warm other | digest | nbytes 0
+IMAGE_HEADER = struct.Struct("<8IQ2I")  # magic version ncat nsym nstate nrange warm other | digest | nbytes flags
+FLAG_CARRY = 1     # header flag bit 0 (KRCA_LOG_FLAG_CARRY): long lines need the state carried between segments
 
 
 class PatternsUnsupported(PatternsChanged):
@@ -77,8 +92,9 @@ def _bracket_end(rx, i):
     return j
 
 
-def _tokens(name, rx):
-    """regex -> tokens ('atom', regex of one code point) | ('q', m, n) | ('|',) | ('(',) | (')',)."""
+def _tokens(name, rx, unbounded=False):
+    """regex -> tokens ('atom', regex of one code point) | ('q', m, n) | ('|',) | ('(',) | (')',);
+    n is None for an unbounded quantifier (taken under ``unbounded`` only)."""
     out, i, n = [], 0, len(rx)
     while i < n:
         ch = rx[i]
@@ -111,18 +127,18 @@ def _tokens(name, rx):
             i += 1
         elif ch in "^$":
             _bad(name, f"anchor '{ch}'")
-        elif ch in "*+":
+        elif ch in "*+" and not unbounded:
             _bad(name, f"unbounded quantifier '{ch}'")
-        elif ch == "?" or (ch == "{" and rx[i + 1:i + 2] != "}" and _BRACES.match(rx, i)):
-            if ch == "?":
-                q, j = (0, 1), i + 1
+        elif ch in "*+?" or (ch == "{" and rx[i + 1:i + 2] != "}" and _BRACES.match(rx, i)):
+            if ch != "{":
+                q, j = {"?": (0, 1), "*": (0, None), "+": (1, None)}[ch], i + 1
             else:  # sre's reading of braces: {m} {m,n} {,n}; {m,} and {,} have no upper bound
                 m = _BRACES.match(rx, i)
                 j = m.end()
                 lo, comma, hi = m.group(1), m.group(2), m.group(3)
-                if comma and not hi:
+                if comma and not hi and not unbounded:
                     _bad(name, f"unbounded quantifier '{rx[i:j]}'")
-                q = (int(lo or 0), int(hi) if comma else int(lo))
+                q = (int(lo or 0), (int(hi) if hi else None) if comma else int(lo))
             if not out or out[-1][0] != "atom":
                 _bad(name, f"quantifier '{rx[i:j]}' on anything but one atom")
             if j < n and rx[j] in "?+":
@@ -138,8 +154,9 @@ def _tokens(name, rx):
     return out
 
 
-def parse(name, rx):
-    """One category's regex -> list of alternatives, each a tuple of atom regexes."""
+def parse(name, rx, unbounded=False):
+    """One category's regex -> list of alternatives, each a tuple of atom regexes.  Under ``unbounded``
+    an item of an alternative may also be a loop item ``("*", atom regex)``."""
     if not isinstance(rx, str):
         _bad(name, f"a pattern of type {type(rx).__name__}")
     try:
@@ -148,7 +165,7 @@ def parse(name, rx):
             re.compile(rx, re.IGNORECASE)
     except (re.error, RecursionError, OverflowError) as e:
         _bad(name, f"a regex re.compile rejects ({e})")
-    toks = _tokens(name, rx)
+    toks = _tokens(name, rx, unbounded)
     if toks and toks[0] == ("(",):  # one outer pair of parentheses
         depth, close = 0, None
         for k, t in enumerate(toks):
@@ -168,6 +185,11 @@ def parse(name, rx):
             cur = [()]
         elif t[0] == "atom":
             m, n = (toks[k + 1][1:] if k + 1 < len(toks) and toks[k + 1][0] == "q" else (1, 1))
+            if n is None:  # x{m,}: m copies of x, then a loop item on x
+                if m > MAX_ALT_LEN:
+                    _bad(name, f"an alternative of more than {MAX_ALT_LEN} code points (a repeat of {m})")
+                cur = [a + (t[1],) * m + (("*", t[1]),) for a in cur]
+                continue
             if m > n:
                 _bad(name, f"quantifier {{{m},{n}}} with min > max")
             if n > MAX_ALT_LEN:
@@ -177,10 +199,11 @@ def parse(name, rx):
                 _bad(name, f"more than {MAX_ALTS} alternatives after expanding quantifiers ({len(cur) + len(alts)}+)")
     alts = list(dict.fromkeys(alts))
     for a in alts:
-        if not a:
+        if not any(isinstance(it, str) for it in a):  # nothing, or loop items only
             _bad(name, "an empty alternative (it matches every line)")
-        if len(a) > MAX_ALT_LEN:
-            _bad(name, f"an alternative of {len(a)} code points (at most {MAX_ALT_LEN})")
+        ncp = sum(isinstance(it, str) for it in a)  # loop items count at their minimum, none
+        if ncp > MAX_ALT_LEN:
+            _bad(name, f"an alternative of {ncp} code points (at most {MAX_ALT_LEN})")
     return alts
 
 
@@ -225,15 +248,16 @@ class LogTables:
 
     FIELDS = ("nsym", "nstate", "ascii_sym", "ranges", "trans", "out", "SEP", "OTHER", "ncat")
 
-    def __init__(self, patterns, warm, **t):
+    def __init__(self, patterns, warm, flags=0, **t):
         self.patterns = tuple(patterns)
         self.names = tuple(n for n, _ in self.patterns)
         self.warm = warm
+        self.flags = flags  # FLAG_CARRY for a set with loop items
         self.digest = pattern_digest(self.patterns)
         self.unidata = unicodedata.unidata_version
         for k in self.FIELDS:
             setattr(self, k, t[k])
-        self._image = None
+        self._image = {}
 
     def __getitem__(self, k):  # the dict form gen_log_dfa.simulate walks
         if k not in self.FIELDS:
@@ -247,41 +271,101 @@ class LogTables:
     def nrange(self):
         return len(self.ranges)
 
-    def image(self):
-        """The flat little-endian table image of include/krca.h (krca_log_tables_check)."""
-        if self._image is None:
+    def image(self, flags=None):
+        """The flat little-endian table image of include/krca.h (krca_log_tables_check).  flags: the
+        header's flag word instead of the set's own (tests force FLAG_CARRY on a fixed-length set to
+        compare the carried long-line kernel with the speculative one)."""
+        flags = self.flags if flags is None else int(flags)
+        if flags not in self._image:
             body = bytes(self.ascii_sym) + np.asarray(self.ranges, "<u4").reshape(-1, 3).tobytes() + \
                 np.asarray(self.trans, "<u2").tobytes() + np.asarray(self.out, "<u2").tobytes()
             body += b"\0" * (-len(body) % 8)
             head = IMAGE_HEADER.pack(IMAGE_MAGIC, IMAGE_VERSION, self.ncat, self.nsym, self.nstate, self.nrange,
-                                     self.warm, self.OTHER, self.digest, IMAGE_HEADER.size + len(body), 0)
-            self._image = head + body
-        return self._image
+                                     self.warm, self.OTHER, self.digest, IMAGE_HEADER.size + len(body), flags)
+            self._image[flags] = head + body
+        return self._image[flags]
+
+
+def _symbol(tables, c):
+    if c < 128:
+        return tables["ascii_sym"][c]
+    ranges = tables["ranges"]
+    sym, lo, hi = tables["OTHER"], 0, len(ranges) - 1
+    while lo <= hi:
+        mid = (lo + hi) >> 1
+        if c < ranges[mid][0]:
+            hi = mid - 1
+        elif c > ranges[mid][1]:
+            lo = mid + 1
+        else:
+            sym = ranges[mid][2]
+            break
+    return sym
 
 
 def simulate(tables, line):
     """Python model of the device matcher on one line (no separators inside) -> category mask."""
     st, m = 0, 0
-    ranges = tables["ranges"]
     for ch in line:
-        c = ord(ch)
-        if c < 128:
-            sym = tables["ascii_sym"][c]
-        else:
-            sym, lo, hi = tables["OTHER"], 0, len(ranges) - 1
-            while lo <= hi:
-                mid = (lo + hi) >> 1
-                if c < ranges[mid][0]:
-                    hi = mid - 1
-                elif c > ranges[mid][1]:
-                    lo = mid + 1
-                else:
-                    sym = ranges[mid][2]
-                    break
+        sym = _symbol(tables, ord(ch))
         assert sym != tables["SEP"]
         st = tables["trans"][st][sym]
         m |= tables["out"][st]
     return m
+
+
+def simulate_segments(tables, line, nseg=64):
+    """Python restatement of log_dfa_long_carry_rt (csrc/log_rt.h) on one line -> (mask, rounds).
+
+    The line's UTF-8 bytes are cut into ``nseg`` segments of ceil(bytes / nseg) bytes; lane i owns
+    the code points whose first byte lies in segment i.  Each lane warms up from the start state
+    over the <= ``warm`` code points before its first one, notes the state it enters its segment
+    with (``entry``), walks to ``exit`` and ORs the masks reported on the way.  Then rounds: ``prev``
+    is the predecessor lane's exit (the start state for lane 0); when no lane has prev != entry the
+    line is done; else every such lane takes prev as its entry and walks its segment again.  An
+    empty segment hands its entry on as its exit.  Masks of superseded walks stay ORed in: every
+    walk starts from the state some suffix of the text before it leads to, so whatever it reports
+    is a match inside the line.  After round r lanes 0..r are final: at most nseg - 1 rounds."""
+    trans, out, warm = tables["trans"], tables["out"], tables.warm
+    syms = [_symbol(tables, ord(ch)) for ch in line]
+    starts, pos = [], 0  # byte offset of each code point
+    for ch in line:
+        starts.append(pos)
+        pos += len(ch.encode("utf-8", "surrogatepass"))
+    seg = (pos + nseg - 1) // nseg
+    first = [0] * (nseg + 1)  # first[i]: index of the first code point starting at or after byte i * seg
+    k = 0
+    for i in range(nseg + 1):
+        while k < len(starts) and starts[k] < min(pos, i * seg):
+            k += 1
+        first[i] = k
+    mask = 0
+
+    def walk(i, st):
+        nonlocal mask
+        for sy in syms[first[i]:first[i + 1]]:
+            st = trans[st][sy]
+            mask |= out[st]
+        return st
+
+    entry, exit_ = [0] * nseg, [0] * nseg
+    for i in range(nseg):
+        st = 0
+        if first[i] > 0 and first[i] < first[i + 1]:
+            for sy in syms[max(0, first[i] - warm):first[i]]:
+                st = trans[st][sy]
+        entry[i] = st
+        exit_[i] = walk(i, st)
+    rounds = 0
+    while True:
+        prev = [0] + exit_[:-1]
+        redo = [i for i in range(nseg) if prev[i] != entry[i]]
+        if not redo:
+            return mask, rounds
+        rounds += 1
+        for i in redo:
+            entry[i] = prev[i]
+            exit_[i] = walk(i, prev[i])
 
 
 def minimize(trans, outs):
@@ -315,19 +399,21 @@ def _limit(what, value, limit):
         raise PatternsUnsupported(f"log pattern set has {value} {what}; the device matcher holds at most {limit}")
 
 
-def compile_patterns(patterns):
-    """Ordered (name, regex) pairs -> LogTables (cached per process by digest)."""
+def compile_patterns(patterns, unbounded=False):
+    """Ordered (name, regex) pairs -> LogTables (cached per process by digest).
+    unbounded: also accept ``* + {m,} {,}`` on one atom (module docstring); a set that uses none of
+    them compiles to the same tables either way."""
     patterns = tuple((str(n), p) for n, p in patterns)
     if not patterns:
         raise PatternsUnsupported("log pattern set is empty")
     _limit("categories", len(patterns), MAX_NCAT)
-    pats = [parse(n, p) for n, p in patterns]  # (also: every regex is a str)
-    key = (pattern_digest(patterns), patterns)
+    pats = [parse(n, p, unbounded) for n, p in patterns]  # (also: every regex is a str)
+    key = (pattern_digest(patterns), patterns)  # (a set with loops gets past parse() only under unbounded)
     hit = _CACHE.get(key)
     if hit is not None:
         return hit
     _limit("alternatives after expansion", sum(len(a) for a in pats), MAX_ALTS)
-    atoms = sorted({a for alts in pats for alt in alts for a in alt})
+    atoms = sorted({(a if isinstance(a, str) else a[1]) for alts in pats for alt in alts for a in alt})
     # signature of a code point: which atoms match it, as bits of Python ints packed in uint64 words
     nw = (len(atoms) + 63) // 64
     sig = np.zeros((MAXCP, nw), np.uint64)
@@ -377,34 +463,62 @@ def compile_patterns(patterns):
         sym_bits[i] = int.from_bytes(s, "little")
     atom_bit = {a: 1 << i for i, a in enumerate(atoms)}
 
-    # ---- subset construction over NFA positions (pattern, alt, offset) -------------------------
-    altbits = [[[atom_bit[a] for a in alt] for alt in alts] for alts in pats]
-    starts = [(p, a, 0) for p, alts in enumerate(pats) for a in range(len(alts))]
+    # ---- subset construction over NFA positions (pattern, alt, item) ------------------------------
+    # An item is an atom or a loop item.  closure(p, a, i): the position and, past every loop item from
+    # it on, the next one.  A loop item that matches the symbol stays (its closure), an atom that matches
+    # advances (the next position's closure); a position at the end of its alternative reports the
+    # category.  Search semantics: the closure of every alternative's position 0 belongs to every state
+    # and is kept out of the state sets.  Positions are numbered and a state is the int of their bits.
+    alts = [(p, [(a if isinstance(a, str) else a[1], not isinstance(a, str)) for a in alt])
+            for p, al in enumerate(pats) for alt in al]
+    base, npos = [], 0
+    for _, items in alts:
+        base.append(npos)
+        npos += len(items) + 1
+    closure, end_cat = [0] * npos, [0] * npos
+    for (p, items), b in zip(alts, base):
+        end_cat[b + len(items)] = 1 << p
+        for i in range(len(items), -1, -1):
+            closure[b + i] = 1 << (b + i)
+            if i < len(items) and items[i][1]:
+                closure[b + i] |= closure[b + i + 1]
+    always = 0
+    for b in base:
+        always |= closure[b]
+    succ = [[0] * npos for _ in range(nsym)]  # succ[sym][position]: where the symbol takes it
+    for (p, items), b in zip(alts, base):
+        for i, (atom, loop) in enumerate(items):
+            bit = atom_bit[atom]
+            for sym in range(nsym):
+                if sym_bits[sym] & bit:
+                    succ[sym][b + i] = closure[b + i] if loop else closure[b + i + 1]
 
-    def step(state, sym):
-        bits, nxt = sym_bits[sym], set()
-        for (p, a, i) in state:
-            alt = altbits[p][a]
-            if i < len(alt) and alt[i] & bits:
-                nxt.add((p, a, i + 1))
-        for (p, a, i) in starts:
-            if altbits[p][a][0] & bits:
-                nxt.add((p, a, 1))
-        return frozenset(nxt)
+    def bits(x):
+        while x:
+            low = x & -x
+            yield low.bit_length() - 1
+            x ^= low
+
+    always_pos = list(bits(always))
+    from_always = [0] * nsym
+    for sym in range(nsym):
+        for q in always_pos:
+            from_always[sym] |= succ[sym][q]
 
     def out(state):
         m = 0
-        for (p, a, i) in state:
-            if i == len(altbits[p][a]):
-                m |= 1 << p
+        for q in bits(state):
+            m |= end_cat[q]
         return m
 
-    start = frozenset()
-    states, order, trans, k = {start: 0}, [start], [], 0
+    states, order, trans, k = {0: 0}, [0], [], 0
     while k < len(order):
-        row = []
+        row, here = [], list(bits(order[k]))
         for sym in range(nsym):
-            nx = step(order[k], sym)
+            nx, sc = from_always[sym], succ[sym]
+            for q in here:
+                nx |= sc[q]
+            nx &= ~always
             if nx not in states:
                 states[nx] = len(order)
                 order.append(nx)
@@ -414,7 +528,12 @@ def compile_patterns(patterns):
         k += 1
     trans, outs = minimize(trans, [out(s) for s in order])
     _limit("states", len(trans), MAX_NSTATE)
-    t = LogTables(patterns, max(len(alt) for alts in pats for alt in alts) - 1, nsym=nsym, nstate=len(trans),
+    loops = any(loop for _, items in alts for _, loop in items)
+    if loops:  # loops at their minimum; only the speculation's warm-up
+        warm = min(63, max(sum(not loop for _, loop in items) for _, items in alts) - 1)
+    else:
+        warm = max(len(items) for _, items in alts) - 1
+    t = LogTables(patterns, warm, flags=FLAG_CARRY if loops else 0, nsym=nsym, nstate=len(trans),
                   ascii_sym=ascii_sym, ranges=ranges, trans=trans, out=outs, SEP=SEP, OTHER=OTHER, ncat=len(pats))
     _CACHE[key] = t
     return t

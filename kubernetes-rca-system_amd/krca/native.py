@@ -160,7 +160,7 @@ class KrcaError(RuntimeError):
 class LogDims(ctypes.Structure):
     """krca_log_dims of include/krca.h: the dimensions of one run-time pattern table."""
     _fields_ = [("ncat", c_i32), ("nsym", c_i32), ("nstate", c_i32), ("nrange", c_i32), ("warm", c_i32),
-                ("other", c_i32), ("digest", ctypes.c_uint64)]
+                ("other", c_i32), ("digest", ctypes.c_uint64), ("flags", ctypes.c_uint32)]
 
 
 class DeviceLogTables:
@@ -866,25 +866,32 @@ class NativeEngine:
                             f"{unicodedata.unidata_version}: regenerate csrc/log_dfa_tables.h "
                             f"(csrc/gen_log_dfa.py) for non-ASCII logs")
 
-    def log_tables(self, patterns):
+    def log_tables(self, patterns, unbounded=False):
         """Compile an ordered sequence of (name, regex) pairs (krca.logdfa.compile_patterns: raises
         PatternsUnsupported outside the subset or the limits), validate the image and upload its
-        device form; cached per engine by pattern digest.  -> DeviceLogTables for ``tables=``."""
+        device form; cached per engine by pattern digest.  -> DeviceLogTables for ``tables=``.
+        unbounded: also take ``* + {m,}`` on one atom; lines over 1 KiB then go through the long-line
+        kernel that carries the state from segment to segment (KRCA_LOG_FLAG_CARRY)."""
         from . import logdfa
-        t = logdfa.compile_patterns(patterns)
+        t = logdfa.compile_patterns(patterns, unbounded=unbounded)
         cache = self.__dict__.setdefault("_log_tables", {})
         hit = cache.get((t.digest, t.patterns))
         if hit is not None:
             return hit
-        image = t.image()
+        cache[(t.digest, t.patterns)] = hit = self.upload_log_tables(t)
+        return hit
+
+    def upload_log_tables(self, t, flags=None):
+        """Validate and upload the image of a krca.logdfa.LogTables (not cached) -> DeviceLogTables.
+        flags: the image's flag word instead of the set's own (LogTables.image(flags=))."""
+        image = t.image(flags)
         dims = check_log_image(image, self.lib)
         dev = self.torch.empty(int(self.lib.krca_log_tables_dev_size(ctypes.byref(dims))), dtype=self.torch.uint8,
                                device=self.device)
         buf = (ctypes.c_char * len(image)).from_buffer_copy(image)
         _check(self.lib.krca_log_tables_upload(buf, len(image), self.ptr(dev), dev.numel(), ctypes.byref(dims),
                                                self._stream()), "krca_log_tables_upload")
-        cache[(t.digest, t.patterns)] = hit = DeviceLogTables(t, dev, dims)
-        return hit
+        return DeviceLogTables(t, dev, dims)
 
     def log_scan_device(self, text, doc_off, validate=True, dense_examples=False, tables=None):
         """text uint8 device tensor (16-byte aligned), doc_off int64 device tensor [D+1].

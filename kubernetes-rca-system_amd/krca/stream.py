@@ -40,7 +40,8 @@ SNAPSHOT_VERSION = 1
 
 class StreamingRCA:
     def __init__(self, engine, row_ptr, col, outdeg, n_metrics, cfg=None, horizon=1440, tol=1e-9, max_iter=100,
-                 check_every=4, comm=None, shard=None, partition=None, timeline=False, gap=3, min_count=3):
+                 check_every=4, comm=None, shard=None, partition=None, timeline=False, gap=3, min_count=3,
+                 log_tables=None):
         """row_ptr / col / outdeg: the whole mesh's pull-CSR (host arrays); this rank keeps its rows.
         comm: krca.rca.Comm (world, rank) — default one rank.  shard: a prepared per-rank backend
         (tests); default DeviceShard on `engine`.  partition: a krca.rca.Partition, or "balanced"
@@ -48,8 +49,12 @@ class StreamingRCA:
         timeline: carry the anomaly timeline's episodes across windows (krca_stream_timeline, gap /
         min_count as krca_rolling_timeline's; an episode is reported for `horizon` steps after its
         last exceedance): every window's scores then hold the six timeline tensors too, and
-        first_movers() ranks them."""
+        first_movers() ranks them.
+        log_tables: a DeviceLogTables (engine.log_tables(patterns[, unbounded=True])): the windows' log
+        text is matched against that pattern set (hist then has its ncat columns) instead of the 13
+        compiled-in patterns; push_logs(tables=) overrides it per call."""
         self.eng = engine
+        self.log_tables = log_tables
         self.cfg = cfg or Config()
         self.comm = comm or Comm()
         self.N = int(len(outdeg))
@@ -136,10 +141,16 @@ class StreamingRCA:
         return self.eng.first_movers(self.last_timeline, *self._csr_dev, slack=slack, k=k, explain=explain)
 
     # -- 2. logs ---------------------------------------------------------------------------------
-    def push_logs(self, text, doc_off, templates=True, validate=True, _defer=False):
+    def push_logs(self, text, doc_off, templates=True, validate=True, _defer=False, tables=None):
         """Window log text of this rank's containers (uint8 device tensor, 16-byte aligned) and its
-        container offsets (int64 device tensor): 13-bin histograms (+ template histograms)."""
-        scan = self.eng.log_scan_device(text, doc_off, validate=validate)
+        container offsets (int64 device tensor): 13-bin histograms (+ template histograms).
+        tables: a DeviceLogTables for this call (default: the stream's log_tables; None there too: the
+        compiled-in patterns, the call as before)."""
+        tables = self.log_tables if tables is None else tables
+        if tables is None:
+            scan = self.eng.log_scan_device(text, doc_off, validate=validate)
+        else:
+            scan = self.eng.log_scan_device(text, doc_off, validate=validate, tables=tables)
         if templates:
             scan["templates"] = self.eng.template_hist_device(scan, defer_huge=_defer)
         return scan
