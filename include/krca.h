@@ -860,6 +860,52 @@ int krca_graph_chain(const int64_t* row_ptr, const int32_t* col, int64_t N, int3
 int krca_graph_cycle(const int64_t* row_ptr, const int32_t* col, int64_t N, int32_t pull, const int32_t* comp,
                      int64_t root, void* ws, int32_t* hop /*[N]*/, int32_t* rounds_host /*[1], nullable*/, void* stream);
 
+/* ---- g1: blast radius of up to 64 sources (the ranked root causes): multi-source reachability over
+ * the dependency graph and the greedy cover of the marked (anomalous) nodes by the sources' radii
+ * (csrc/graph_reach.hip; a caller of the reference could only run nx.ancestors per
+ * candidate on the host).  Graph arguments and `pull` as krca_graph_scc: either layout, duplicate
+ * edges and self-loops legal, a col entry outside [0, N) is no edge and never used as an index.
+ * dir: KRCA_REACH_DEPENDENTS = bits flow against the edges (who transitively calls the source),
+ * KRCA_REACH_DEPENDENCIES = along them (what the source transitively calls).
+ * KRCA_EINVAL before any device work: K outside [1, 64], H outside [2, 64], dir or pull outside {0, 1},
+ * a src_host[k] outside [0, N), N > 2^31 - 2, and N == 0 (no source can be valid).  Duplicate sources
+ * are legal: each gets its own bit and identical results.  mark (uint8 [N], device) == NULL means every
+ * node is marked, in both calls.  Both calls SYNCHRONISE the stream: the levels (and the cover's
+ * steps) are plain launches driven from the host, which reads a "changed" word per level (64 counters
+ * per step) back; the level loop gives up after N + 2 rounds with KRCA_ENOTCONV.
+ *
+ * krca_graph_reach: with d_k(v) = the BFS distance from src[k] to v in direction dir (0 at the source;
+ *   infinite when v is unreachable, or beyond max_hops when max_hops > 0; max_hops <= 0 = unbounded):
+ *   reach[v] bit k = d_k(v) is finite, bits K..63 are 0;
+ *   hist_host[0][k][h] = the nodes with d_k = h for h < H - 1, the last bin (h = H - 1) the nodes with
+ *   finite d_k >= H - 1;  hist_host[1][k][h] = the same over the nodes with mark != 0;
+ *   depth_host[k] = the largest finite d_k;  rounds_host[1] (nullable) = the levels run (informational).
+ *   Every output is a function of the edge set, the sources and mark alone: either layout, any row
+ *   order, and dir swapped together with the transposed arrays give identical bytes.
+ * krca_graph_reach_cover: greedy set cover of the marked nodes by the sources' radii.  Step j picks the
+ *   k with the largest gain = the marked v that have bit k of reach[v] and no previously chosen bit
+ *   (ties: the lowest k) and stops when the largest gain is 0:  order_host[j], gain_host[j] = the pick
+ *   and its gain, unused slots -1 and 0;  exclusive_host[k] = the marked v with reach[v] == 1 << k;
+ *   totals_host[2] = {marked nodes, marked nodes with reach != 0}.  Bits K..63 of reach are ignored.
+ *   One count launch and one read-back per step.
+ * Buffers: reach [N] is fully written by krca_graph_reach (it is the BFS's "seen" word).  ws
+ *   (krca_graph_reach_ws_size(N) bytes, 8-byte aligned, for both calls) needs no initialisation: each
+ *   call zeroes the control words, histogram bins and counters it reads back, and krca_graph_reach
+ *   writes both per-node frontier words for all N nodes before a level reads them.
+ *   Not for graph capture (memsets, read-backs). */
+#define KRCA_REACH_MAX_SRC 64
+#define KRCA_REACH_DEPENDENTS 0
+#define KRCA_REACH_DEPENDENCIES 1
+int64_t krca_graph_reach_ws_size(int64_t N);
+int krca_graph_reach(const int64_t* row_ptr, const int32_t* col, int64_t N, int32_t pull,
+                     const int32_t* src_host /*[K]*/, int32_t K, int32_t dir, int32_t max_hops,
+                     const uint8_t* mark /*[N] device, nullable*/, int32_t H, void* ws,
+                     uint64_t* reach /*[N] device*/, int64_t* hist_host /*[2][K][H]*/,
+                     int32_t* depth_host /*[K]*/, int32_t* rounds_host /*[1], nullable*/, void* stream);
+int krca_graph_reach_cover(const uint64_t* reach, const uint8_t* mark /*nullable*/, int64_t N, int32_t K,
+                           void* ws, int32_t* order_host /*[K]*/, int64_t* gain_host /*[K]*/,
+                           int64_t* exclusive_host /*[K]*/, int64_t* totals_host /*[2]*/, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,7 +23,7 @@ from .traces import TracesAgent
 
 class Coordinator:
     def __init__(self, k8s_client, engine=None, rank_config=None, correlations=False, corr_channel=0, corr_span=None,
-                 corr_max_lag=8, corr_tau=0.5, corr_slack=0):
+                 corr_max_lag=8, corr_tau=0.5, corr_slack=0, blast_radius=False, blast_bins=16):
         from krca.rca import RANKING
         self.k8s_client = k8s_client
         self._engine = engine
@@ -33,6 +33,11 @@ class Coordinator:
         self.correlations = bool(correlations)
         self.corr_params = {'channel': int(corr_channel), 'span': None if corr_span is None else int(corr_span),
                             'max_lag': int(corr_max_lag), 'tau': float(corr_tau), 'slack': int(corr_slack)}
+        # blast_radius=True: the additive key "blast_radius" (what each ranked root cause takes down:
+        # krca_graph_reach / krca_graph_reach_cover over the dependency graph)
+        self.blast_radius = bool(blast_radius)
+        self.blast_bins = int(blast_bins)
+        self._rank_ctx = None
         self.metrics_agent = MetricsAgent(k8s_client, engine, window=self.rank_config.window,
                                           z_threshold=self.rank_config.z_threshold)
         self.logs_agent = LogsAgent(k8s_client, engine)
@@ -79,6 +84,8 @@ class Coordinator:
         ranked = self._rank_root_causes(namespace)
         if ranked is not None:
             out['ranked_root_causes'] = ranked
+        if self.blast_radius and ranked:
+            out['blast_radius'] = self._blast_radius()
         if self.correlations:
             corr = self._correlations(namespace, ranked)
             if corr is not None:
@@ -158,9 +165,19 @@ class Coordinator:
                 for i in pods if i in lr['explained']]
         return {'lead_roots': roots, 'followers': foll, 'params': dict(p)}
 
+    # -- additive blast radius ----------------------------
+    def _blast_radius(self):
+        """Per ranked root cause: its transitive dependents, how many of them are anomalous and at
+        which hop; the greedy cover of the anomalous nodes by the candidates' radii."""
+        x = self._rank_ctx
+        br = self.engine.blast_radius(x['row_ptr'], x['col'], x['idx'], pull=True, direction='dependents',
+                                      bins=self.blast_bins, **x['mark'])
+        return br.summary(names=[x['prefix'] + n for n in x['names']])
+
     # -- additive ranking ----------------------------------------------------------------
     def _rank_root_causes(self, namespace):
         c = self.k8s_client
+        self._rank_ctx = None
         scores = self.metrics_agent.last_scores
         if scores is not None and hasattr(c, 'get_dependency_csr'):
             names, row_ptr, col, outdeg = c.get_dependency_csr(namespace)
@@ -168,6 +185,9 @@ class Coordinator:
             idx, val, rank = self.engine.rank_root_causes(scores['score'], row_ptr, col, outdeg, self.rank_config,
                                                           n_metrics=int(zl.shape[1]) if zl is not None else 1)
             sc = np.asarray(scores['score'].cpu() if hasattr(scores['score'], 'cpu') else scores['score'])
+            self._rank_ctx = {'prefix': 'Pod/', 'names': names, 'row_ptr': row_ptr, 'col': col, 'idx': idx,
+                              'mark': {'score': scores['score'], 'floor': self.rank_config.floor(
+                                  len(outdeg), int(zl.shape[1]) if zl is not None else 1)}}
             return [{'component': f"Pod/{names[i]}", 'rank': r + 1, 'score': float(v), 'pagerank': float(rank[i]),
                      'anomaly': float(sc[i])} for r, (i, v) in enumerate(zip(idx.tolist(), val.tolist()))]
         if hasattr(c, 'get_service_dependencies') and hasattr(c, 'get_error_rate_by_service'):
@@ -187,6 +207,8 @@ class Coordinator:
                 return None
             idx, val, rank = self.engine.rank_root_causes(seed, row_ptr, col, outdeg,
                                                           self.rank_config.replace(seed_floor=0.0))
+            self._rank_ctx = {'prefix': 'Service/', 'names': names, 'row_ptr': row_ptr, 'col': col, 'idx': idx,
+                              'mark': {'mark': seed > 0}}
             return [{'component': f"Service/{names[i]}", 'rank': r + 1, 'score': float(v), 'pagerank': float(rank[i]),
                      'anomaly': float(seed[i])} for r, (i, v) in enumerate(zip(idx.tolist(), val.tolist()))]
         return None

@@ -146,6 +146,10 @@ SIGNATURES = {
     "krca_graph_scc": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "krca_graph_chain": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "krca_graph_cycle": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    "krca_graph_reach_ws_size": (c_i64, [c_i64]),
+    "krca_graph_reach": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_vp, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp,
+                                 c_vp, c_vp]),
+    "krca_graph_reach_cover": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
 }
 
 KRCA_ENOTCONV = -70
@@ -572,6 +576,80 @@ class NativeEngine:
         elif cycle:
             gs.hop = np.full(N, -1, np.int32)
         return gs
+
+    # -- g1 blast radius: multi-source reachability and greedy cover (csrc/graph_reach.hip) ------------
+    def graph_reach_device(self, rp, cl, N, pull, sources, direction=0, max_hops=0, mark=None, bins=16, cover=True):
+        """Device CSR tensors, host source ids [K], mark uint8 device tensor [N] or None -> dict: reach
+        (int64 device tensor [N] holding the uint64 words), hist int64 [2][K][H], depth int32 [K], rounds, and
+        with cover: order int32 [K], gain / exclusive int64 [K], totals int64 [2] (host).  SYNCHRONISES."""
+        src = np.ascontiguousarray(sources, np.int32)
+        K, H = int(len(src)), int(bins)
+        reach = self.torch.empty(max(N, 1), dtype=self.torch.int64, device=self.device)
+        ws = self._workspace("graph_reach", self.lib.krca_graph_reach_ws_size(N))
+        hist = np.zeros((2, max(K, 1), max(H, 1)), np.int64)
+        depth = np.zeros(max(K, 1), np.int32)
+        rounds = (c_i32 * 1)()
+        vp = ctypes.c_void_p
+        mp = self.ptr(mark) if mark is not None else None
+        _check(self.lib.krca_graph_reach(self.ptr(rp), self.ptr(cl), N, int(pull), src.ctypes.data_as(vp), K,
+                                         int(direction), int(max_hops), mp, H, self.ptr(ws), self.ptr(reach),
+                                         hist.ctypes.data_as(vp), depth.ctypes.data_as(vp), rounds, self._stream()),
+               "krca_graph_reach")
+        out = {"reach": reach, "hist": hist[:, :K, :H], "depth": depth[:K], "rounds": int(rounds[0])}
+        if cover:
+            out.update(self.graph_reach_cover_device(reach, mark, N, K))
+        return out
+
+    def graph_reach_cover_device(self, reach, mark, N, K):
+        """reach as graph_reach_device returned it -> dict: order int32 [K], gain / exclusive int64 [K], totals
+        int64 [2] (host).  SYNCHRONISES."""
+        vp = ctypes.c_void_p
+        order, gain, excl = np.zeros(K, np.int32), np.zeros(K, np.int64), np.zeros(K, np.int64)
+        totals = np.zeros(2, np.int64)
+        ws = self._workspace("graph_reach", self.lib.krca_graph_reach_ws_size(N))
+        _check(self.lib.krca_graph_reach_cover(self.ptr(reach), self.ptr(mark) if mark is not None else None, N, K,
+                                               self.ptr(ws), order.ctypes.data_as(vp), gain.ctypes.data_as(vp),
+                                               excl.ctypes.data_as(vp), totals.ctypes.data_as(vp), self._stream()),
+               "krca_graph_reach_cover")
+        return dict(order=order, gain=gain, exclusive=excl, totals=totals)
+
+    def blast_radius(self, row_ptr, col, sources, mark=None, score=None, floor=None, pull=True, direction="dependents",
+                     max_hops=0, bins=16, cover=True):
+        """What each of up to 64 sources takes down: CSR (host or device arrays, layout as graph_structure)
+        -> krca.blast.BlastRadius (host arrays).  direction "dependents": who transitively calls a source,
+        "dependencies": what it transitively calls.  mark (uint8 / bool [N]) selects the nodes the marked
+        histograms and the cover count; with score and floor instead, mark = score > floor is made on the
+        device; neither: every node.  -1 entries of sources (a top-k with fewer than k keys) are dropped."""
+        from .blast import DIRECTIONS, BlastRadius
+        torch = self.torch
+        if direction not in DIRECTIONS:
+            raise KrcaError(f"blast_radius: direction must be one of {sorted(DIRECTIONS)}")
+        N = int(len(row_ptr)) - 1
+        if N < 1:
+            raise KrcaError("blast_radius: the graph has no node")
+        rp, cl = self._dev_n(row_ptr, np.int64), self._dev_n(col, np.int32)
+        if rp.dtype != torch.int64 or cl.dtype != torch.int32:
+            raise KrcaError("blast_radius: row_ptr must be int64 and col int32")
+        src = np.asarray(sources.cpu() if isinstance(sources, torch.Tensor) else sources, np.int64).reshape(-1)
+        src = src[src != -1]
+        if score is not None and floor is not None:
+            sc = self._dev(score) if isinstance(score, torch.Tensor) else self._dev(np.asarray(score, np.float32))
+            mark = (sc.reshape(-1)[:N] > float(np.float32(floor))).to(torch.uint8)  # the float32 floor the ranking used
+        elif mark is not None:
+            if isinstance(mark, torch.Tensor):
+                mark = (mark.to(self.device) != 0).to(torch.uint8).contiguous()
+            else:
+                mark = self._dev((np.asarray(mark).reshape(-1) != 0).astype(np.uint8))
+            if int(mark.numel()) != N:
+                raise KrcaError("blast_radius: mark must have N entries")
+        o = self.graph_reach_device(rp, cl, N, int(bool(pull)), src, DIRECTIONS[direction], max_hops, mark, bins, cover)
+        reach = o["reach"][:N].cpu().numpy().view(np.uint64)
+        br = BlastRadius(reach, o["hist"][0].copy(), o["hist"][1].copy(), o["depth"].copy(), sources=src.astype(np.int32),
+                         direction=direction, max_hops=int(max_hops), rounds=o["rounds"])
+        if cover:
+            br.order, br.gain, br.exclusive = o["order"], o["gain"], o["exclusive"]
+            br.n_marked, br.n_covered = int(o["totals"][0]), int(o["totals"][1])
+        return br
 
     # -- f2 service-graph construction --------------------------------------------------------
     def selector_match(self, lab, lab_off, sel, sel_off):
