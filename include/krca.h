@@ -906,6 +906,67 @@ int krca_graph_reach_cover(const uint64_t* reach, const uint8_t* mark /*nullable
                            void* ws, int32_t* order_host /*[K]*/, int64_t* gain_host /*[K]*/,
                            int64_t* exclusive_host /*[K]*/, int64_t* totals_host /*[2]*/, void* stream);
 
+/* ---- a13b: log-template novelty across windows (csrc/template_novelty.hip, csrc/tmpl_novelty_layout.h,
+ * DESIGN.md §3.18; the reference keeps no log state between two analyses).  A device-resident table maps
+ * the exact key (group int32 >= 0, template hash uint64) to the record {first_win, last_win, n_win,
+ * total int64}; a record with n_win == 0 is absent.  tests/template_novelty_ref.py restates the
+ * semantics on the host; every quantity is an integer and the device equals it bit for bit.
+ *
+ * One window w (the caller passes strictly increasing windows): the entries are, for every container d
+ * of [0, ndocs) with group[d] >= 0 (group == NULL: every container in group 0) and j < n_templates[d],
+ * the triple (group[d], tmpl_hash[doc_line0[d] + j], tmpl_count[doc_line0[d] + j]) as krca_template_hist
+ * left them (after krca_template_hist_huge); an entry with count <= 0, or whose slot lies outside
+ * [0, n_lines), is skipped and its slot never read.  A hash equal to the table's empty marker (2^64 - 1)
+ * is counted under 2^64 - 2.  Per key: cur_lines = the sum of the counts, cur_docs = the entries
+ * showing it (the containers: krca_template_hist lists a hash once per container; arrays that list one
+ * twice count it twice), first_doc = the lowest such d.  cur_lines and cur_docs share one 64-bit word
+ * (40 + 24 bits): a key whose counts sum to 2^40 or more in one window is outside the contract -- its
+ * record and report are then UNDEFINED (never a fault); 2^40 lines exceed any window's n_lines here.  With `absent` = n_win == 0, or ttl > 0 and
+ * last_win < w - ttl (the history is then discarded; ttl == 0 never expires):
+ *   NOVEL (flag 1): absent;   SURGE (flag 2): present, cur_lines >= surge_min and
+ *   cur_lines * (w - first_win) >= surge_ratio * total (exact 128-bit products, total before w).
+ * Commit: first_win = w if absent, last_win = w, n_win = 1 if absent else n_win + 1, total (0 if absent)
+ * += cur_lines.  report == 0 commits and flags nothing (n_novel = n_surge = n_reported = 0, doc_* = 0).
+ *
+ * counts_host[6] = {n_entries, n_keys_touched, n_novel, n_surge, n_reported, n_live_slots (records
+ *   with n_win > 0 in the table, those whose ttl ran out untouched included)}; read back synchronously
+ *   (the call SYNCHRONISES the stream once, as krca_log_scan).
+ * report_out: cap records of 48 bytes {uint64 hash, int64 total_before, int64 cur_lines, int32 group,
+ *   flags, cur_docs, first_doc, first_win (w when novel), pad}, one per NOVEL or SURGE key in any order;
+ *   min(n_reported, cap) are written, all distinct; the counts stay exact beyond cap.
+ * doc_novel / doc_surge (int32 [ndocs], each nullable): the container's entries whose key is NOVEL /
+ *   SURGE this window; every element written.
+ * KRCA_ENOMEM: a key found no slot.  The records are then exactly those before the call (slots claimed
+ *   by the failed window stay behind as absent records); rehash into a larger table and repeat.
+ * krca_template_novelty_rehash: new_state (krca_template_novelty_state_size(new_capacity) bytes, needs
+ *   no initialisation, must not overlap old_state) receives every record with n_win > 0 and
+ *   last_win >= min_last_window; KRCA_ENOMEM when they do not fit.  Synchronises.
+ * KRCA_EINVAL before any device work: a capacity that is no power of two in [64, 2^30]; negative ndocs,
+ *   n_lines, window, ttl or cap; ndocs > 2^24 - 1; surge_ratio < 1 or surge_min < 1; report != 0 with
+ *   cap > 0 and a null report_out; a null state or counts_host.  ndocs == 0 is a valid empty window.
+ *   A state that krca_template_novelty_init did not write: no kernel touches it past its first 256
+ *   bytes, KRCA_EINVAL after the read-back.
+ * Buffers: state = krca_template_novelty_state_size(capacity) bytes, 8-byte aligned, fully defined by
+ *   krca_template_novelty_init (the touched list behind the slots is written before it is read).  The
+ *   update needs no initialisation of its outputs.  Not for graph capture (a read-back).
+ * krca_template_novelty_layout(which): 0 header bytes, 1 slot bytes, 2 report record bytes, 3 bits of
+ *   cur_lines in the packed per-window word, 4 the largest ndocs; krca_template_novelty_home_slot: the
+ *   slot a key's probe starts at (-1 for a bad capacity or group); host functions for the mirror in
+ *   krca/novelty.py. */
+int64_t krca_template_novelty_layout(int32_t which);
+int64_t krca_template_novelty_home_slot(uint64_t hash, int32_t group, int64_t capacity);
+int64_t krca_template_novelty_state_size(int64_t capacity);
+int krca_template_novelty_init(void* state, int64_t capacity, void* stream);
+int krca_template_novelty_update(void* state, const uint64_t* tmpl_hash, const int32_t* tmpl_count, int64_t n_lines,
+                                 const int32_t* n_templates, const int64_t* doc_line0,
+                                 const int32_t* group /*[ndocs], nullable*/, int64_t ndocs, int32_t window, int32_t ttl,
+                                 int32_t surge_ratio, int32_t surge_min, int32_t report,
+                                 void* report_out /*cap records, device*/, int32_t cap,
+                                 int32_t* doc_novel /*[ndocs], nullable*/, int32_t* doc_surge /*[ndocs], nullable*/,
+                                 int64_t* counts_host /*[6]*/, void* stream);
+int krca_template_novelty_rehash(const void* old_state, void* new_state, int64_t new_capacity, int32_t min_last_window,
+                                 void* stream);
+
 #ifdef __cplusplus
 }
 #endif

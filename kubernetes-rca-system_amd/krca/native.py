@@ -150,9 +150,17 @@ SIGNATURES = {
     "krca_graph_reach": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_vp, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp,
                                  c_vp, c_vp]),
     "krca_graph_reach_cover": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "krca_template_novelty_layout": (c_i64, [c_i32]),
+    "krca_template_novelty_home_slot": (c_i64, [ctypes.c_uint64, c_i32, c_i64]),
+    "krca_template_novelty_state_size": (c_i64, [c_i64]),
+    "krca_template_novelty_init": (c_i32, [c_vp, c_i64, c_vp]),
+    "krca_template_novelty_update": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_i32,
+                                             c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    "krca_template_novelty_rehash": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_vp]),
 }
 
 KRCA_ENOTCONV = -70
+KRCA_ENOMEM = -12
 PPR_RESIDUAL, PPR_WRITE_R = 1, 2  # krca_ppr_shard_step flags
 SCORE_VARIANTS = {0: "pipe", 1: "ring", 3: "reread", 4: "pipe_rows"}  # krca_rolling_score_variant (2, 5: retired)
 

@@ -16,7 +16,9 @@ pull-CSR.
 2. The window's log text of the rank's containers goes through krca_log_scan
    (13-pattern histograms per container, the reference's LogsAgent semantics,
    ref:agents/logs_agent.py:147-151) and krca_template_hash / krca_template_hist (error-template
-   histograms per container).  No communication.
+   histograms per container).  No communication.  With novelty=True the window's template
+   histograms then update a device-resident novelty table (krca/novelty.py, krca_template_novelty_update):
+   templates never logged before, known ones that surged, and the containers showing them.
 3. PageRank is re-seeded with the new scores and warm-started from the previous window's ranks
    (krca_ppr_shard_init_warm), iterating to the networkx L1 stop rule with ONE all-gather per
    iteration (Comm.exchange; G = 1: a buffer swap); the root-cause top-k merges G x k candidates.
@@ -41,7 +43,7 @@ SNAPSHOT_VERSION = 1
 class StreamingRCA:
     def __init__(self, engine, row_ptr, col, outdeg, n_metrics, cfg=None, horizon=1440, tol=1e-9, max_iter=100,
                  check_every=4, comm=None, shard=None, partition=None, timeline=False, gap=3, min_count=3,
-                 log_tables=None):
+                 log_tables=None, novelty=None, container_group=None, novelty_warmup=0):
         """row_ptr / col / outdeg: the whole mesh's pull-CSR (host arrays); this rank keeps its rows.
         comm: krca.rca.Comm (world, rank) — default one rank.  shard: a prepared per-rank backend
         (tests); default DeviceShard on `engine`.  partition: a krca.rca.Partition, or "balanced"
@@ -52,7 +54,23 @@ class StreamingRCA:
         first_movers() ranks them.
         log_tables: a DeviceLogTables (engine.log_tables(patterns[, unbounded=True])): the windows' log
         text is matched against that pattern set (hist then has its ncat columns) instead of the 13
-        compiled-in patterns; push_logs(tables=) overrides it per call."""
+        compiled-in patterns; push_logs(tables=) overrides it per call.
+        novelty: True, or a dict of krca.novelty.TemplateNovelty's arguments: every window()'s error
+        templates go through a device-resident novelty table and the window's
+        NoveltyReport -- templates never logged before, known ones that surged, and how many of each
+        every container shows -- is out["logs"]["novelty"].  container_group: int32 per container (its
+        service id, say): templates are then new per group instead of cluster-wide.  The first
+        novelty_warmup windows only learn.  One rank only: the key space is not sharded by container."""
+        self.novelty, self.novelty_warmup, self._container_group = None, int(novelty_warmup), None
+        if novelty is not None and novelty is not False:
+            if (comm.world if comm is not None else 1) > 1:
+                raise ValueError("StreamingRCA: novelty runs on one rank (world == 1): the template table is not sharded")
+            from .novelty import TemplateNovelty
+            self.novelty = TemplateNovelty(engine, **(novelty if isinstance(novelty, dict) else {}))
+            if container_group is not None:
+                cg = container_group
+                self._container_group = engine._dev(cg, engine.torch.int32) if isinstance(cg, engine.torch.Tensor) \
+                    else engine._dev(np.asarray(cg, np.int32))
         self.eng = engine
         self.log_tables = log_tables
         self.cfg = cfg or Config()
@@ -260,6 +278,10 @@ class StreamingRCA:
             self.eng.template_hist_finish(tm)  # synchronises main (after side)
         else:
             main.synchronize()
+        if self.novelty is not None and templates:
+            w = self.novelty.last_window + 1
+            logs["novelty"] = self.novelty.update(tm, logs["doc_line0"], group=self._container_group, window=w,
+                                                  report=w >= self.novelty_warmup)
         out["logs"] = logs
         return out
 
@@ -270,6 +292,8 @@ class StreamingRCA:
                     cfg=self.cfg.as_dict(), tol=self.tol)
         if self.timeline:  # a stream without the timeline writes the keys it always wrote
             meta.update(timeline=True, gap=self.gap, min_count=self.min_count)
+        if self.novelty is not None:  # likewise: the key exists only on a stream with the novelty table
+            meta.update(novelty=dict(self.novelty.params(), warmup=self.novelty_warmup))
         return meta
 
     def snapshot(self, path):
@@ -281,6 +305,8 @@ class StreamingRCA:
         investigations only (ref:utils/db_handler.py:13); this is the stream's own checkpoint."""
         meta = dict(self._meta(), t=self.t, solved=self.solved, last_iters=self.last_iters)
         arrays = self.shard.state_dict(self.M, self.H)
+        if self.novelty is not None:
+            arrays.update(self.novelty.state_dict())
         blob = np.frombuffer(json.dumps(meta, sort_keys=True).encode(), np.uint8)
         with open(path, "wb") as f:
             np.savez(f, meta=blob, **arrays)
@@ -295,10 +321,16 @@ class StreamingRCA:
         diff = sorted(k for k in want if meta.get(k) != want[k])
         if bool(meta.get("timeline", False)) != self.timeline and "timeline" not in diff:
             diff.append("timeline")  # a timeline snapshot into a stream without one
+        if ("novelty" in meta) != (self.novelty is not None) and "novelty" not in diff:
+            diff.append("novelty")  # a novelty snapshot into a stream without the table
         if diff:
             raise ValueError(f"snapshot {path} does not match this stream: {', '.join(diff)} differ")
         if self.timeline and "episode_state" not in arrays:
             raise ValueError(f"snapshot {path} holds no episode state")
+        if self.novelty is not None:
+            if "novelty_slots" not in arrays:
+                raise ValueError(f"snapshot {path} holds no novelty table")
+            self.novelty.load_state_dict(arrays)
         self.shard.load_state_dict(arrays, self.M, self.H)
         self.last_timeline = None  # the next window writes it
         self.t, self.solved, self.last_iters = int(meta["t"]), bool(meta["solved"]), int(meta["last_iters"])
