@@ -69,7 +69,9 @@ int krca_usage_flags(const float* usage /*[P][2]*/, int64_t P, uint8_t* flags /*
  * ref:agents/metrics_agent.py:44-47).  x is time-major [T][P][M] float32 (series s = p*M+m).
  * For t in [W, T), over the trailing window x[t-W..t-1] (float64 sliding sums s1, s2 in a fixed
  * order): A = W*x_t - s1, B = W*s2 - s1^2 (= W^2 var, ddof 0), z = A/sqrt(B) = (x_t - mean)/std;
- * exceed(t) = B > 1e-12*W^2 && A^2 > z_thr^2 * B.   Outputs:
+ * exceed(t) = B > 1e-12*W^2 && A^2 > z_thr^2 * B.  z_thr is float32 in every scoring call (the
+ * rolling and the stream ones): a binding that holds a float64 threshold rounds it to float32, and
+ * z_thr^2 is the float64 square of that float32 value.   Outputs:
  *   z_last[p][m] = z at t = T-1 (0 if B <= 1e-12*W^2),   score[p] = max_m |z_last|,
  *   n_exceed[p]  = sum over m, t of exceed(t) (bit-exact vs oracle/krca_oracle.c),
  *   flags[p]     = KRCA_F_* of x[T-1][p][0] (CPU %) and x[T-1][p][1] (memory %) if M >= 2.

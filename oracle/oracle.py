@@ -118,6 +118,26 @@ def template_hist(text):
     return sorted(cnt.items())
 
 
+def template_hist_slots(hash_, doc_lines, doc_line0, fill_hash, fill_count):
+    """What krca_template_hist (+ _huge) leave in tmpl_hash / tmpl_count / n_templates for given line
+    hashes (uint64 [L]) and per-container line ranges [doc_line0[d], doc_line0[d] + doc_lines[d]):
+    the container's distinct hashes ascending with their counts, then zeros up to its last line; a
+    slot in no range keeps the fill values.  -> (tmpl_hash uint64 [L], tmpl_count int32 [L],
+    n_templates int32 [D])."""
+    hash_ = np.asarray(hash_, np.uint64)
+    oh = np.full(len(hash_), fill_hash, np.uint64)
+    oc = np.full(len(hash_), fill_count, np.int32)
+    nt = np.zeros(len(doc_lines), np.int32)
+    for d, (n, lo) in enumerate(zip(np.asarray(doc_lines).tolist(), np.asarray(doc_line0).tolist())):
+        u, c = np.unique(hash_[lo:lo + n], return_counts=True)
+        nt[d] = len(u)
+        oh[lo:lo + n] = 0
+        oc[lo:lo + n] = 0
+        oh[lo:lo + len(u)] = u
+        oc[lo:lo + len(u)] = c
+    return oh, oc, nt
+
+
 # ------------------------------------------------------------------------------------------
 # rolling z-score (a5), float64 independent formulation (prefix sums)
 # ------------------------------------------------------------------------------------------
@@ -169,7 +189,8 @@ def ppr_f64(row_ptr, col, outdeg, seed, alpha=0.85, max_iter=100, tol=1e-6):
 def topk_ref(v, k):
     """Descending, ties -> lower index (the device contract)."""
     v = np.asarray(v)
-    order = np.lexsort((np.arange(len(v)), -v.astype(np.float64) if v.dtype.kind == "f" else -v))
+    # integers descend by ~v = -v - 1: -v wraps INT64_MIN onto itself and would rank it first
+    order = np.lexsort((np.arange(len(v)), -v.astype(np.float64) if v.dtype.kind == "f" else ~v))
     idx = order[:k]
     return idx.astype(np.int32), v[idx]
 

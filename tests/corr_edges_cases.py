@@ -134,3 +134,51 @@ def tol(T):
     """|r - ref| bound of the issue: float32 accumulation in any order errs by at most T u sum|ab| / T
     with sum|ab| / T <= 1 for standardised rows (Cauchy-Schwarz), plus two final roundings."""
     return (T + 2) * 2.0 ** -24
+
+
+# ---- launch forms of krca_corr_edges ---------------------------------------------------------------
+# (T, L) at N = 40.  A wave's LDS row holds stride = T + 2 LT floats rounded up to 4 (LT = L rounded
+# up to 0 / 4 / 8 / 16); a workgroup runs four waves while 4 rows fit 64 KiB, else one; a call whose
+# single row does not fit is refused; 16-byte loads need T % 4 == 0 and a 16-byte-aligned z.
+LAUNCH_N = 40
+LAUNCH_SHAPES = [(4080, 8), (4081, 8), (4084, 8), (16368, 8), (16384, 0), (4068, 16)]
+REFUSED_SHAPES = [(16369, 8), (16385, 0), (16353, 16)]
+MISALIGNED_T = (64, 4084)
+LAUNCH_TAU = 0.125  # below the scale of c = S / T on these rows (variance 24: |c| ~ 24 / sqrt(T) >= 0.18)
+LDS_BYTES = 65536
+
+
+def launch_form(T, L, aligned=True):
+    """-> (waves per workgroup, bytes per load) krca_corr_edges takes for these sizes by the rule of
+    include/krca.h, or None when the call is refused."""
+    lt = 0 if L == 0 else 4 if L <= 4 else 8 if L <= 8 else 16
+    stride = (T + 2 * lt + 3) & ~3
+    if 4 * stride > LDS_BYTES:
+        return None
+    return (4 if 16 * stride <= LDS_BYTES else 1), (16 if T % 4 == 0 and aligned else 4)
+
+
+def launch_case(T):
+    """dyadic_case(T, N = 40) without the tie list, computed once per T."""
+    if T not in _launch_cache:
+        z, rp, col, _ = dyadic_case(T, N=LAUNCH_N)
+        _launch_cache[T] = (z, rp, col)
+    return _launch_cache[T]
+
+
+_launch_cache = {}
+
+
+# ---- follower clamp of krca_corr_lead_key ----------------------------------------------------------
+CLAMP = (1 << 20) - 1
+FOLLOWERS = (0, 1, CLAMP - 1, CLAMP, CLAMP + 1, CLAMP + 6, 2 ** 31 - 1)
+DENORMAL = float(np.float32(2.0 ** -149))
+KEY_SCORES = (0.0, DENORMAL, 1.5, float("inf"), float("nan"), -1.0)
+
+
+def lead_key_case():
+    """Fabricated inputs of krca_corr_lead_key: FOLLOWERS x dep_lead in {0, 1} x KEY_SCORES
+    -> (dep_lead int32, caller_follow int32, score float32)."""
+    rows = [(d, f, s) for f in FOLLOWERS for d in (0, 1) for s in KEY_SCORES]
+    d, f, s = (np.array(c) for c in zip(*rows))
+    return d.astype(np.int32), f.astype(np.int32), s.astype(np.float32)

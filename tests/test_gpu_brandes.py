@@ -60,6 +60,61 @@ def test_betweenness_exact_ties_and_degenerate(eng):
     _check(eng, nx.empty_graph(4, create_using=nx.DiGraph))
 
 
+def _check_scaling(eng, g, normalized, batch=1024):
+    """Either scaling against networkx at the tolerances of _check; unnormalized values are pair
+    counts, so the absolute part scales with the largest of them."""
+    nodes = list(g.nodes)
+    rp, col = _csr(g, nodes)
+    got = eng.betweenness(rp, col, normalized=normalized, directed=g.is_directed(), batch=batch)
+    ref = nx.betweenness_centrality(g, normalized=normalized)
+    want = np.array([ref[n] for n in nodes])
+    assert got.shape == want.shape
+    atol = 1e-15 * (1.0 if normalized else max(1.0, float(want.max(initial=0.0))))
+    assert np.allclose(got, want, rtol=1e-12, atol=atol), (normalized, g.is_directed(), batch, np.max(np.abs(got - want)))
+    return got, want
+
+
+@pytest.mark.parametrize("batch", [1, 7, 1024])
+@pytest.mark.parametrize("directed", [True, False])
+@pytest.mark.parametrize("normalized", [True, False])
+def test_betweenness_every_scaling(eng, normalized, directed, batch):
+    """(normalized, directed) in all four combinations: 1 / ((n - 1)(n - 2)), the undirected 1 / 2 and
+    no scaling at all, at source batches of 1, 7 and more than the graph."""
+    for n, p, seed in ((30, 0.1, 1), (300, 0.02, 5)):
+        got, want = _check_scaling(eng, nx.gnp_random_graph(n, p, seed=seed, directed=directed), normalized, batch)
+        assert want.max() > 0
+    # N = 1, 2, 3: the n > 2 edge of the normalization
+    kind = nx.DiGraph if directed else nx.Graph
+    for edges, n in (([], 1), ([(0, 1)], 2), ([(0, 1), (1, 2)], 3)):
+        g = nx.empty_graph(n, create_using=kind)
+        g.add_edges_from(edges)
+        got, want = _check_scaling(eng, g, normalized, batch)
+        if n < 3:
+            assert not got.any()
+        else:  # the middle of the chain: 1 ordered pair directed, 2 / 2 undirected; (n - 1)(n - 2) = 2
+            assert got.tolist() == [0.0, 0.5 if normalized and directed else 1.0, 0.0]
+
+
+@pytest.mark.parametrize("normalized", [True, False])
+def test_betweenness_self_loops_are_ignored(eng, normalized):
+    g = nx.gnp_random_graph(60, 0.06, seed=8, directed=True)
+    plain = _check_scaling(eng, g, normalized)[0]
+    g.add_edges_from((v, v) for v in range(0, 60, 3))
+    assert nx.number_of_selfloops(g) == 20
+    looped = _check_scaling(eng, g, normalized)[0]
+    assert np.array_equal(looped, plain) and plain.max() > 0
+
+
+def test_betweenness_unnormalized_exact(eng):
+    """Paths of 5 nodes: node i lies between i (4 - i) pairs, counted once per unordered pair
+    (undirected: both directions, halved) and once per ordered pair along the chain (directed)."""
+    path = nx.path_graph(5)
+    chain = nx.DiGraph([(i, i + 1) for i in range(4)])
+    for g in (path, chain):
+        got, want = _check_scaling(eng, g, False)
+        assert got.tolist() == [0.0, 3.0, 4.0, 3.0, 0.0] == want.tolist()
+
+
 def test_betweenness_20k_path_length_identity(eng):
     from scipy.sparse import csr_matrix
     from scipy.sparse.csgraph import shortest_path

@@ -72,6 +72,68 @@ def test_dyadic_long_row(eng, L):
     assert ref["caller_follow"][n] + ref["caller_sync"][n] + ref["caller_lead"][n] > C.CHUNK
 
 
+# ---- launch forms: one wave per workgroup, the largest T, a misaligned z ----------------------------
+@pytest.mark.parametrize("T,L", C.LAUNCH_SHAPES)
+def test_launch_forms_match_reference(eng, T, L):
+    """T + 2 LT around 4096 (four waves per workgroup -> one) and at the 16384-float limit of a
+    wave's LDS row, with 4-byte and 16-byte loads: bit-equal on integer rows (|S| <= 64 T < 2^24)."""
+    assert C.launch_form(T, L) is not None
+    z, rp, col = C.launch_case(T)
+    ref = check_exact(eng, z, rp, col, L, tau=C.LAUNCH_TAU, slack=1 if L >= 2 else 0)
+    if L > 0:  # (tests/test_argument_cases_cpu.py holds the counts the reference finds)
+        assert ref["dep_lead"].sum() > 100 and ref["caller_lead"].sum() > 100
+
+
+@pytest.mark.parametrize("T,L", C.REFUSED_SHAPES)
+def test_launch_refused_past_the_largest_T(eng, T, L):
+    assert C.launch_form(T, L) is None and C.launch_form(T - 1, L) is not None
+    zd = torch.zeros((C.LAUNCH_N, T), dtype=torch.float32, device="cuda")
+    rpd, cld = eng._csr_dev(*C.launch_case(64)[1:])
+    with pytest.raises(native.KrcaError, match=f"T={T}"):
+        eng.corr_edges_device(zd, rpd, cld, L, C.LAUNCH_TAU, 0)
+
+
+@pytest.mark.parametrize("T", C.MISALIGNED_T)
+def test_misaligned_z_takes_the_4_byte_loads(eng, T):
+    """T % 4 == 0 with z 4-byte but not 16-byte aligned: byte-equal to the aligned call and the reference."""
+    z, rp, col = C.launch_case(T)
+    score = np.random.default_rng(T).integers(-16, 160, len(z)).astype(np.float32) / 16
+    ref = R.edges(z, rp, col, 8, C.LAUNCH_TAU, 1)
+    ref["key"] = R.lead_key(ref["dep_lead"], ref["caller_follow"], score)
+    rpd, cld = eng._csr_dev(rp, col)
+    sd = torch.from_numpy(score).cuda()
+    buf = torch.empty(z.size + 4, dtype=torch.float32, device="cuda")
+    assert buf.data_ptr() % 16 == 0
+    outs = []
+    for shift in (0, 1, 2, 3):
+        zd = buf[shift:shift + z.size].view(z.shape)
+        zd.copy_(torch.from_numpy(z))
+        assert zd.data_ptr() % 16 == 4 * shift and zd.is_contiguous()
+        out = eng.corr_edges_device(zd, rpd, cld, 8, C.LAUNCH_TAU, 1)
+        got = {k: v.cpu().numpy() for k, v in out.items()}
+        got["key"] = eng.corr_lead_key_device(out, sd).cpu().numpy()
+        outs.append(got)
+    for shift, got in enumerate(outs):
+        for name in ALL + ("key",):
+            assert same(got[name], ref[name]), (name, shift)
+            assert same(got[name], outs[0][name]), (name, shift)
+
+
+# ---- the follower clamp of the key -----------------------------------------------------------------
+def test_lead_key_follower_clamp(eng):
+    """Fabricated counts around 2^20 - 1 (the key's follower field holds 20 bits) crossed with dep_lead,
+    and scores 0, denormal, 1.5, inf, NaN and -1: bit-equal to the reference's formula."""
+    d, f, s = C.lead_key_case()
+    out = dict(dep_lead=torch.from_numpy(d).cuda(), caller_follow=torch.from_numpy(f).cuda())
+    key = eng.corr_lead_key_device(out, torch.from_numpy(s).cuda()).cpu().numpy()
+    ref = R.lead_key(d, f, s)
+    assert same(key, ref), np.flatnonzero(key != ref)[:5]
+    at = lambda fv: key[(d == 0) & (f == fv) & (s == np.float32(1.5))][0]  # noqa: E731
+    assert at(C.CLAMP + 1) == at(C.CLAMP + 6) == at(2 ** 31 - 1) == at(C.CLAMP)  # counts above the clamp tie
+    assert 0 < at(1) < at(C.CLAMP - 1) < at(C.CLAMP)
+    assert (key[np.isnan(s) | (s <= 0) | (d != 0) | (f == 0)] == 0).all() and (key >= 0).all()
+
+
 def test_no_edges(eng):
     z = C.dyadic_case(64, N=40)[0]
     got = run(eng, z, np.zeros(41, np.int64), np.zeros(0, np.int32), 8, score=np.ones(40, np.float32))

@@ -7,6 +7,7 @@ import pytest
 import torch
 
 import oracle
+import timeline_cases as TC
 from krca import native, synth
 from krca.agents.logs import pack_documents
 
@@ -102,7 +103,73 @@ def test_rolling_score_deterministic_and_planted_roots(eng):
     assert set(idx.tolist()) == set(m.roots.tolist())
 
 
+THR_FORMS = [(60, 0, "pipe"), (60, 4, "pipe_rows"), (60, 1, "ring"), (7, 0, "reread")]  # (W, KRCA_SCORE_IMPL, variant)
+
+
+@pytest.mark.parametrize("W,impl,variant", THR_FORMS, ids=[f[2] for f in THR_FORMS])
+@pytest.mark.parametrize("thr", TC.THRS)
+def test_rolling_score_thresholds(eng, thr, W, impl, variant):
+    """Thresholds off 3.0, most of them not float32 values, in every kernel form: the four outputs
+    equal the C twin's bit for bit, and n_exceed equals the independent float64 count (taken at the
+    threshold float32 holds) on every pod where the two host references agree -- all but 0.5 % of the
+    pods (tests/test_argument_cases_cpu.py: none differ at this shape)."""
+    P, M, T, _ = TC.THR_SHAPE
+    x = TC.threshold_series()
+    twin, n64, agree = TC.threshold_refs(W, thr)
+    assert (~agree).sum() <= TC.THR_MAX_DISAGREE * P
+    with native.tune(eng.lib, KRCA_SCORE_IMPL=impl):
+        assert native.SCORE_VARIANTS[eng.lib.krca_rolling_score_variant(P, M, T, W)] == variant
+        got = eng.rolling_score_device(torch.from_numpy(np.array(x)).cuda(), W, thr)  # (a writable copy)
+    for k in ("n_exceed", "flags", "z_last", "score"):
+        g = got[k].cpu().numpy()
+        assert g.dtype == twin[k].dtype and g.shape == twin[k].shape, k
+        bad = np.flatnonzero((g.view(np.uint32) != twin[k].view(np.uint32)) if g.dtype == np.float32 else (g != twin[k]))
+        assert len(bad) == 0, (k, thr, variant, bad[:5], g.reshape(-1)[bad[:5]], twin[k].reshape(-1)[bad[:5]])
+    n = got["n_exceed"].cpu().numpy()
+    assert np.array_equal(n[agree], n64[agree])
+
+
 # ---- top-k -----------------------------------------------------------------------------------
+def _topk_padded(v, k):
+    """oracle.topk_ref, with the slots past the keys as the device leaves them: index -1, lowest key."""
+    ridx, rval = oracle.topk_ref(v, k)
+    low = -np.inf if v.dtype.kind == "f" else np.iinfo(np.int64).min
+    pad = k - len(ridx)
+    return np.concatenate([ridx, np.full(pad, -1, np.int32)]), np.concatenate([rval, np.full(pad, low, v.dtype)])
+
+
+def _check_topk(eng, v, k):
+    idx, val = eng.topk(torch.from_numpy(v), k)
+    ridx, rval = _topk_padded(v, k)
+    assert idx.tolist() == ridx.tolist(), (len(v), k)
+    assert val.dtype == v.dtype and val.tobytes() == rval.tobytes(), (len(v), k)  # -0.0 stays -0.0
+    return ridx
+
+
+@pytest.mark.parametrize("N", [5, 1000, 70_000])
+@pytest.mark.parametrize("k", [11, 15])
+def test_topk_sixteen_entry_network_below_its_size(eng, N, k):
+    """11 <= k <= 15 runs the 16-entry insertion network with k below its size (k <= 10 has its own)."""
+    rng = np.random.default_rng(N + k)
+    _check_topk(eng, rng.integers(0, 4, N).astype(np.float32), k)            # many ties
+    z = rng.choice(np.array([-0.0, 0.0], np.float32), N)                      # the two zeros tie: by index
+    assert _check_topk(eng, z, k).tolist()[:min(N, k)] == list(range(min(N, k)))
+    z[rng.integers(0, N, 3)] = 1.0
+    z[0] = -1.0
+    _check_topk(eng, z, k)
+    # INT64_MIN is a key like any other: taken with its index, by index among its equals, before any
+    # -1 slot (whose value is INT64_MIN too)
+    lo = np.iinfo(np.int64).min
+    vi = np.full(N, lo, np.int64)
+    above = rng.choice(N, min(N - 1, 7), replace=False)
+    vi[above] = rng.integers(lo + 1, lo + 4, len(above))                      # fewer than k keys above it, with ties
+    ridx = _check_topk(eng, vi, k)
+    assert sorted(ridx[:len(above)].tolist()) == sorted(above.tolist())
+    assert (ridx[len(above):min(N, k)] >= 0).all() and (ridx[min(N, k):] == -1).all()
+    vi[above[:3]] = np.iinfo(np.int64).max
+    _check_topk(eng, vi, k)
+
+
 @pytest.mark.parametrize("N,k", [(1, 1), (10, 10), (1000, 10), (1 << 20, 10), (3_000_001, 16), (777, 5)])
 def test_topk_float_and_int(eng, N, k):
     rng = np.random.default_rng(N)
@@ -956,6 +1023,102 @@ def test_template_hist_writes_every_slot(eng):
     for d in range(len(docs)):
         assert (ohn[d0[d] + n[d]:d0[d] + dl[d]] == 0).all() and (ocn[d0[d] + n[d]:d0[d] + dl[d]] == 0).all(), d
         assert (ocn[d0[d]:d0[d] + n[d]] > 0).all(), d
+
+
+# krca_template_hist on GIVEN hashes: the path boundaries and the values the sorts use as padding
+TMPL_SIZES = (0, 1, 7, 8, 9, 63, 64, 65, 255, 256, 257, 1023, 1024, 1025, 4095, 4096, 4097)
+TMPL_PAD = 2 ** 64 - 1  # what the sorts pad with; 0 is what fills the slots past the templates
+TMPL_SPECIAL = (0, 1, 2 ** 63, TMPL_PAD - 1, TMPL_PAD)
+TMPL_PAIRS = ((0, TMPL_PAD), (TMPL_PAD - 1, TMPL_PAD), (1, 2 ** 63))
+TMPL_POISON_H, TMPL_POISON_C = -0x5A5A5A5A5A5A5A5B, -0x5A5A5A5B
+_tmpl_layouts = {}
+
+
+def _distinct_hashes(rng, n):
+    """n distinct uint64 values: the special ones first (as many as fit), random ones after, shuffled."""
+    r = np.setdiff1d(np.unique(rng.integers(0, 2 ** 64, 2 * n + 8, dtype=np.uint64)), np.array(TMPL_SPECIAL, np.uint64))
+    out = np.concatenate([np.array(TMPL_SPECIAL, np.uint64), rng.permutation(r)])[:n]
+    return rng.permutation(out)
+
+
+def _ranges(sizes, gap=0, reverse=False):
+    """doc_line0 of containers of these sizes laid one after another (gap unused lines between two),
+    in list order or with the last container first; -> (doc_line0 int64 [D], lines in all)."""
+    sizes = np.asarray(sizes, np.int64)
+    order = np.arange(len(sizes))[::-1] if reverse else np.arange(len(sizes))
+    d0 = np.zeros(len(sizes), np.int64)
+    at = 0
+    for d in order.tolist():
+        d0[d] = at
+        at += int(sizes[d]) + gap
+    return d0, max(at, 1)
+
+
+def template_layouts():
+    """name -> (hash uint64 [L], doc_lines int32 [D], doc_line0 int64 [D]), built once."""
+    if _tmpl_layouts:
+        return _tmpl_layouts
+    rng = np.random.default_rng(17)
+    conts = []
+    for n in TMPL_SIZES:  # every size all-equal (each special value), all-distinct, and of two values
+        conts += [np.full(n, v, np.uint64) for v in TMPL_SPECIAL]
+        conts.append(_distinct_hashes(rng, n))
+        conts += [rng.choice(np.array(p, np.uint64), n) for p in TMPL_PAIRS]
+    pool = np.concatenate([np.array(TMPL_SPECIAL, np.uint64), rng.integers(0, 2 ** 64, 3, dtype=np.uint64)])
+    small = lambda sizes: [rng.choice(pool, n) for n in sizes]  # noqa: E731  (repeats inside a container)
+
+    def put(name, conts_, gap=0, reverse=False):
+        dl = np.array([len(c) for c in conts_], np.int32)
+        d0, L = _ranges(dl, gap, reverse)
+        h = rng.integers(0, 2 ** 64, L, dtype=np.uint64)  # lines in no range hold hashes too
+        for c, lo in zip(conts_, d0.tolist()):
+            h[lo:lo + len(c)] = c
+        _tmpl_layouts[name] = (h, dl, d0)
+
+    put("order", conts)
+    put("gaps", conts, gap=3)
+    put("reverse", conts, reverse=True)
+    put("span1024", small([4] * 256))                       # a staged block of exactly 1024 lines
+    put("span1025", small([4] * 255 + [5]))                 # one line more: not staged
+    mixed = [4] * 256
+    mixed[100], mixed[200] = 9, 65                          # wave and workgroup containers among lane ones
+    put("mixed1090", small(mixed))
+    mixed = [4] * 188 + [3] * 66 + [9, 65]                  # the same inside a staged block: 1024 lines
+    put("mixed1024", small([mixed[i] for i in rng.permutation(256)]))
+    return _tmpl_layouts
+
+
+@pytest.mark.parametrize("name", ["order", "gaps", "reverse", "span1024", "span1025", "mixed1090", "mixed1024"])
+def test_template_hist_on_given_hashes(eng, name):
+    """Line counts at 8 / 9, 64 / 65 and 4096 / 4097, the 1024-line staging limit of a 256-container
+    block, line ranges with gaps and in reverse order, and hashes equal to the sorts' pad value and to
+    the filler 0: every slot of every range, n_templates, and every slot outside the ranges (poison
+    kept) equal oracle.template_hist_slots."""
+    h, dl, d0 = template_layouts()[name]
+    D, L = len(dl), len(h)
+    hd = torch.from_numpy(h.view(np.int64)).cuda()
+    scan = dict(doc_lines=torch.from_numpy(dl).cuda(), doc_line0=torch.from_numpy(d0).cuda())
+    oh = torch.full((L,), TMPL_POISON_H, dtype=torch.int64, device="cuda")
+    oc = torch.full((L,), TMPL_POISON_C, dtype=torch.int32, device="cuda")
+    nt = torch.full((D,), TMPL_POISON_C, dtype=torch.int32, device="cuda")
+    ws = eng._workspace("tmpl_hist_t", eng.lib.krca_template_hist_ws_size(D)).view(torch.int32)
+    assert eng.lib.krca_template_hist(eng.ptr(hd), eng.ptr(scan["doc_lines"]), eng.ptr(scan["doc_line0"]), D,
+                                      eng.ptr(ws), eng.ptr(oh), eng.ptr(oc), eng.ptr(nt), eng._stream()) == 0
+    eng._template_huge(ws, hd, oh, oc, nt, scan)
+    torch.cuda.synchronize()
+    # the paths taken: the lists' counts in the workspace (mid <= 64 < big <= 4096 < huge)
+    assert ws[:3].tolist() == [int(((dl > 8) & (dl <= 64)).sum()), int(((dl > 64) & (dl <= 4096)).sum()),
+                               int((dl > 4096).sum())]
+    rh, rc, rn = oracle.template_hist_slots(h, dl, d0, np.int64(TMPL_POISON_H).astype(np.uint64), TMPL_POISON_C)
+    gh, gc, gn = oh.cpu().numpy().view(np.uint64), oc.cpu().numpy(), nt.cpu().numpy()
+    assert np.array_equal(gn, rn), np.flatnonzero(gn != rn)[:5]
+    for d in np.flatnonzero((gh != rh) | (gc != rc))[:1].tolist():
+        c = int(np.searchsorted(np.sort(d0), d, side="right")) - 1
+        raise AssertionError((name, "slot", d, "range", c, hex(int(gh[d])), hex(int(rh[d])), int(gc[d]), int(rc[d])))
+    inside = np.zeros(L, bool)
+    for n, lo in zip(dl.tolist(), d0.tolist()):
+        inside[lo:lo + n] = True
+    assert (gc[~inside] == TMPL_POISON_C).all() and (name != "gaps" or (~inside).sum() >= 3 * (D - 1))
 
 
 def test_template_hash_any_line_order(eng):

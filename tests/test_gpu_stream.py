@@ -12,6 +12,7 @@ import pytest
 import torch
 
 import oracle
+import timeline_cases as TC
 from krca import native, synth
 from krca.rca import Config
 from krca.stream import StreamingRCA
@@ -47,6 +48,82 @@ def test_stream_score_equals_batch_prefix(eng, H):
         want = _n_prefix(x, t, W) - _n_prefix(x, t - H, W) if t - H > W else _n_prefix(x, t, W)
         assert np.array_equal(o["n_exceed"].cpu().numpy(), want), t
     assert t == T
+
+
+def _stream_rows(eng, x, W, H, thr, wins, episodes):
+    """One krca_stream_score (or, episodes: krca_stream_timeline with gap 3, min_count 3) stream over
+    x in calls of `wins` steps at threshold thr -> per window a dict of host arrays."""
+    T, P, M = x.shape
+    t, lib, p = torch, eng.lib, eng.ptr
+    new = lambda dt, *shape: t.empty(shape or (P,), dtype=dt, device=eng.device)  # noqa: E731
+    state = new(t.uint8, int(lib.krca_stream_state_size(P, M, W, H)))
+    ep_state = new(t.uint8, int(lib.krca_stream_episode_state_size(P, M)))
+    xd = t.from_numpy(np.array(x)).cuda()
+    rows, t0 = [], 0
+    for d in wins:
+        o = dict(z_last=new(t.float32, P, M), score=new(t.float32), n_exceed=new(t.int32), flags=new(t.uint8))
+        four = (p(o["z_last"]), p(o["score"]), p(o["n_exceed"]), p(o["flags"]))
+        if episodes:
+            o.update(onset=new(t.int32), last=new(t.int32), count=new(t.int32), peak=new(t.float32), lead=new(t.int8),
+                     n_metrics=new(t.uint8))
+            rc = lib.krca_stream_timeline(p(xd[t0:t0 + d]), P, M, d, t0, W, H, thr, 3, 3, p(state), p(ep_state), *four,
+                                          p(o["onset"]), p(o["last"]), p(o["count"]), p(o["peak"]), p(o["lead"]),
+                                          p(o["n_metrics"]), eng._stream())
+        else:
+            rc = lib.krca_stream_score(p(xd[t0:t0 + d]), P, M, d, t0, W, H, thr, p(state), *four, eng._stream())
+        native._check(rc, "krca_stream_timeline" if episodes else "krca_stream_score")
+        t0 += d
+        rows.append({k: v.cpu().numpy() for k, v in o.items()})
+    return rows
+
+
+@pytest.mark.parametrize("H", TC.THR_STREAM_HORIZONS)
+@pytest.mark.parametrize("thr", TC.THR_STREAM_THRS)
+def test_stream_score_thresholds(eng, thr, H):
+    """Thresholds off 3.0 (2.7 is no float32 value) through krca_stream_score, horizons of whole
+    exceedance-bit words (32, 64) and a partial one (50): after every window what
+    test_stream_score_equals_batch_prefix asserts, with the threshold passed to the C twin."""
+    P, M, T, W = TC.THR_SHAPE
+    x = TC.threshold_series()
+    n_prefix = lambda t: (oracle.c_rolling_score(x[:t], W, thr)["n_exceed"] if t > W  # noqa: E731
+                          else np.zeros(P, np.int32))
+    t = 0
+    for d, o in zip(TC.THR_STREAM_WINDOWS, _stream_rows(eng, x, W, H, thr, TC.THR_STREAM_WINDOWS, False)):
+        t += d
+        ref = oracle.c_rolling_score(x[:t], W, thr)
+        assert np.array_equal(o["flags"], ref["flags"]), t
+        assert np.allclose(o["z_last"], ref["z_last"], rtol=1e-5, atol=1e-6), t
+        assert np.allclose(o["score"], ref["score"], rtol=1e-5, atol=1e-6), t
+        want = n_prefix(t) - n_prefix(t - H) if t - H > W else n_prefix(t)
+        assert np.array_equal(o["n_exceed"], want), t
+    assert t == T and t - H > W and want.sum() > 0
+
+
+@pytest.mark.parametrize("H", TC.THR_STREAM_HORIZONS)
+@pytest.mark.parametrize("thr", TC.THR_STREAM_THRS)
+def test_stream_timeline_thresholds(eng, thr, H):
+    """The same through krca_stream_timeline on the series rounded to 1/16 (the NumPy reference is
+    exact there): the six episode outputs bit-equal to tests/stream_timeline_ref.py after every window,
+    the four scoring outputs bit-equal to a parallel krca_stream_score stream, n_exceed to the twin."""
+    import stream_timeline_ref as SR
+    P, M, T, W = TC.THR_SHAPE
+    x = np.ascontiguousarray(TC.threshold_series(dyadic=True)[:, :TC.THR_STREAM_PODS])
+    wins = TC.THR_STREAM_WINDOWS
+    ref = TC.threshold_stream_ref(thr, H)
+    got = _stream_rows(eng, x, W, H, thr, wins, True)
+    sc = _stream_rows(eng, x, W, H, thr, wins, False)
+    n_prefix = lambda t: (oracle.c_rolling_score(x[:t], W, thr)["n_exceed"] if t > W  # noqa: E731
+                          else np.zeros(x.shape[1], np.int32))
+    t = 0
+    for i, d in enumerate(wins):
+        t += d
+        for k in SR.KEYS:
+            assert got[i][k].dtype == ref[i][k].dtype and got[i][k].tobytes() == ref[i][k].tobytes(), (k, t)
+        for k in ("z_last", "score", "n_exceed", "flags"):
+            assert got[i][k].tobytes() == sc[i][k].tobytes(), (k, t)
+        want = n_prefix(t) - n_prefix(t - H) if t - H > W else n_prefix(t)
+        assert np.array_equal(got[i]["n_exceed"], want), t
+    assert (ref[-1]["onset"] >= 0).any()
 
 
 def test_stream_windows_rerank_warm_started(eng):

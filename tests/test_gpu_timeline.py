@@ -76,6 +76,39 @@ def test_timeline_per_row_descriptors(eng):
         check_timeline(eng, x, 60, 3.0, 3, 3, "ring")
 
 
+@pytest.mark.parametrize("W,variant", [(10, "pipe"), (7, "reread")])
+@pytest.mark.parametrize("thr", C.THR_STREAM_THRS)
+def test_timeline_thresholds(eng, thr, W, variant):
+    """Thresholds off 3.0 / 2.5 (2.7 is no float32 value and its square is not dyadic; 0.5 makes most
+    steps exceed, so episodes chain and split everywhere) on the threshold series rounded to 1/16."""
+    ref = check_timeline(eng, np.array(C.threshold_series(dyadic=True)), W, thr, 3, 3, variant)
+    assert (ref["onset"] >= 0).sum() > 5  # (tests/test_argument_cases_cpu.py: the reference alone)
+
+
+def test_first_mover_key_follower_clamp(eng):
+    """Fabricated follower counts around 2^20 - 1 (the key's follower field holds 20 bits), alone and
+    as sums of two counts below it, crossed with dep_earlier, onset and peak: bit-equal to the
+    reference's formula; counts above the clamp tie, 2^20 - 2 still ranks below 2^20 - 1."""
+    onset, peak, prec = C.first_mover_key_case()
+    dev = {k: torch.from_numpy(v).cuda() for k, v in prec.items()}
+    key = eng.first_mover_key_device(torch.from_numpy(onset).cuda(), torch.from_numpy(peak).cuda(), dev).cpu().numpy()
+    ref = R.first_mover_key(onset, peak, prec)
+    assert key.dtype == ref.dtype and np.array_equal(key, ref), np.flatnonzero(key != ref)[:5]
+
+    def at(later, conc):
+        sel = (onset == 5) & (prec["dep_earlier"] == 0) & (peak == np.float32(1.5)) \
+            & (prec["caller_later"] == later) & (prec["caller_concurrent"] == conc)
+        return int(key[sel][0])
+
+    top = at(C.CLAMP, 0)
+    assert top == (C.CLAMP << 32) | int(np.float32(1.5).view(np.uint32))
+    assert at(C.CLAMP + 1, 0) == at(C.CLAMP + 6, 0) == at(2 ** 31 - 1, 0) == at(0, C.CLAMP + 1) == top
+    assert at(1 << 19, 1 << 19) == at(C.CLAMP, C.CLAMP) == at(2 ** 31 - 1, 2 ** 31 - 1) == top
+    assert at(1 << 19, (1 << 19) - 1) == at(C.CLAMP - 1, 1) == at(1, C.CLAMP - 1) == top
+    assert 0 < at(1, 0) < at(C.CLAMP - 1, 0) == at(1 << 19, (1 << 19) - 2) < top
+    assert (key[(onset < 0) | (prec["dep_earlier"] != 0)] == 0).all()
+
+
 def test_timeline_hand_fixture(eng):
     x = C.episode_fixture()
     ref = check_timeline(eng, x, C.W, C.THR, C.G, C.MINC, "pipe")

@@ -1,9 +1,11 @@
 """Trace analytics on the device (csrc/trace.hip): every output bit-exact against tests/trace_ref.py."""
+import ctypes
 import json
 import os
 
 import numpy as np
 import pytest
+import torch
 
 import agent_cases as A
 import trace_ref
@@ -162,6 +164,76 @@ def test_stats_and_quantiles(eng, lds_max, N, S_kind):
     # 0 = by size; 1 = LDS tables (small S only); 2 = folded global atomics; 3 = one atomic set per lane
     impls = (0, 1, 2, 3) if S <= lds_max else (0, 2, 3)
     _check_stats(eng, slot, val, flags, S, impls)
+
+
+# permille lists off (500, 900, 950, 990): one entry, the two ends, unsorted, and the limit of 16
+# entries, descending with repeats
+PERMILLE_LISTS = [(1,), (1000,), (1, 500, 1000), (999, 1000, 1, 2),
+                  (1000, 1000, 999, 990, 950, 950, 900, 750, 500, 500, 250, 100, 10, 2, 1, 1)]
+FORCED_COUNTS = (1, 999, 1000, 1001, 2000)  # the rank k = (q n + 999) / 1000 around n = 1000
+
+
+def _forced_case(N, S, n_forced):
+    """_stats_case with the records of slot S - 1 replaced by exactly n_forced records."""
+    slot, val, flags = _stats_case(N, S)
+    rng = np.random.default_rng(n_forced + S)
+    slot[slot == S - 1] = -1
+    slot = np.concatenate([slot, np.full(n_forced, S - 1, np.int32)])
+    val = np.concatenate([val, (2.0 ** rng.uniform(0, 32, n_forced)).astype(np.uint64).clip(0, 2 ** 32 - 1).astype(np.uint32)])
+    flags = np.concatenate([flags, np.zeros(n_forced, np.uint8)])
+    order = rng.permutation(len(slot))
+    return slot[order], val[order], flags[order]
+
+
+@pytest.mark.parametrize("N", [1, 65, 5000])
+@pytest.mark.parametrize("S_kind", ["1", "lds_max", "lds_max+1", "300"])
+def test_quantiles_permille_lists(eng, lds_max, N, S_kind):
+    S = {"1": 1, "lds_max": lds_max, "lds_max+1": lds_max + 1, "300": 300}[S_kind]
+    assert len(PERMILLE_LISTS[-1]) == 16
+    for n_forced in FORCED_COUNTS:
+        slot, val, flags = _forced_case(N, S, n_forced)
+        rrec, rhist = trace_ref.stats(slot, val, flags, S)
+        assert rrec[S - 1, 0] == n_forced
+        rec, hist = eng.trace_stats_device(eng._dev_n(slot, np.int32), eng._dev_n(val, np.uint32),
+                                           eng._dev_n(flags, np.uint8), len(slot), S)
+        assert np.array_equal(rec[:S].cpu().numpy(), rrec) and np.array_equal(hist[:S].cpu().numpy().view(np.uint32), rhist)
+        for permille in PERMILLE_LISTS:
+            q = eng.trace_quantiles_device(rec, hist, S, permille)[:S].cpu().numpy().view(np.uint32)
+            rq = trace_ref.quantiles(rrec, rhist, permille)
+            assert q.shape == rq.shape and np.array_equal(q, rq), (n_forced, permille)
+            true = trace_ref.true_quantiles(slot, val, S, permille)
+            b = trace_ref.quantile_bucket(rrec, rhist, permille)
+            lo = np.where(b >= 0, trace_ref.LO[np.maximum(b, 0)], 0)
+            assert (lo <= true).all() and (true <= rq).all(), (n_forced, permille)
+            if permille == (1, 500, 1000):  # the smallest value's bucket, and exactly the largest value
+                v = np.sort(val[slot == S - 1].astype(np.int64))
+                assert rq[S - 1, 2] == v[-1] and trace_ref.bucket(v[0]) == b[S - 1, 0]
+                assert true[S - 1, 1] == v[(500 * n_forced + 999) // 1000 - 1]
+
+
+def test_quantiles_refusals(eng):
+    """permille outside [1, 1000] and Q outside [1, 16]: KRCA_EINVAL naming the argument, nothing written."""
+    slot, val, flags = _stats_case(100, 5)
+    rec, hist = eng.trace_stats_device(eng._dev_n(slot, np.int32), eng._dev_n(val, np.uint32),
+                                       eng._dev_n(flags, np.uint8), 100, 5)
+    out = torch.full((5 * 17,), 0x5B5B5B5B, dtype=torch.int32, device="cuda")
+
+    def call(permille):
+        q = (ctypes.c_int32 * max(len(permille), 1))(*permille)
+        return eng.lib.krca_trace_quantiles(eng.ptr(rec), eng.ptr(hist), 5, q, len(permille), eng.ptr(out), eng._stream())
+
+    for permille, word in (((0,), b"permille[0]=0"), ((500, 1001), b"permille[1]=1001"), ((500, -1, 2), b"permille[1]=-1"),
+                           ((), b"Q=0"), ((500,) * 17, b"Q=17")):
+        assert call(permille) == -22 and word in eng.lib.krca_last_error(), (permille, eng.lib.krca_last_error())
+    with pytest.raises(native.KrcaError):
+        eng.trace_quantiles_device(rec, hist, 5, (1001,))
+    torch.cuda.synchronize()
+    assert bool((out == 0x5B5B5B5B).all().item())  # no refused call launched anything
+    assert call((500,) * 16) == 0  # the limit itself is accepted
+    torch.cuda.synchronize()
+    want = trace_ref.quantiles(*trace_ref.stats(slot, val, flags, 5), (500,) * 16)
+    assert np.array_equal(out[:80].cpu().numpy().view(np.uint32).reshape(5, 16), want)
+    assert bool((out[80:] == 0x5B5B5B5B).all().item())
 
 
 def test_stats_hot_slots_50k(eng):

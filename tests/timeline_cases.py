@@ -131,3 +131,82 @@ class BulkClient(DictClient):
 
     def get_pod_metric_tensor(self, ns):
         return self.names, self.x
+
+
+# ---- scorer threshold cases -------------------------------------------------------------------
+# Thresholds that float32 does not hold exactly (2.7, 3.3, 1.1, 1e-3), ones it does (0.5, 0.0, 1000.0),
+# one that nearly everything exceeds (1e-3), the strict `>` at 0.0 and one nothing reaches (1000.0).
+THRS = (2.7, 3.3, 1.1, 0.5, 1e-3, 0.0, 1000.0)
+THR_SHAPE = (300, 8, 200, 60)  # P, M, T, W
+THR_WINDOWS = (60, 7)          # W = 60: the kernels of pipe_window(); W = 7: the re-reading kernel
+THR_STREAM_WINDOWS = [1, 7, 45, 60, 87]
+THR_STREAM_HORIZONS = (50, 32, 64)  # 32 and 64: whole exceedance-bit words
+THR_STREAM_THRS = (2.7, 0.5)
+THR_MAX_DISAGREE = 0.005  # share of pods on which the C twin and the float64 reference may differ
+# sum over pods of the float64 reference's n_exceed at W = 60, recorded from the two host references
+THR_TOTALS_W60 = {2.7: 4692, 3.3: 988, 0.5: 218754, 1e-3: 335748, 0.0: 336000, 1000.0: 0}
+_thr_cache = {}
+
+
+def threshold_series(dyadic=False):
+    """x float32 [T, P, M] of the threshold cases, read-only and shared; dyadic: the same series
+    rounded to multiples of 1/16 in [0, 100] (timeline_ref.quantise), on which the NumPy timeline
+    references are exact for any threshold: A^2 is exact, and both sides round thr^2 B once."""
+    from krca import synth
+    if "x" not in _thr_cache:
+        P, M, T_, W_ = THR_SHAPE
+        m = synth.make_graph(P, 8, seed=3)
+        x = synth.make_metrics(P, M, T_, window=W_, seed=4, roots=m.roots).numpy().copy()
+        xq = R.quantise(x)
+        x.setflags(write=False)
+        xq.setflags(write=False)
+        _thr_cache["x"], _thr_cache["xq"] = x, xq
+    return _thr_cache["xq" if dyadic else "x"]
+
+
+def threshold_refs(W_, thr):
+    """-> (the C twin's dict, the float64 reference's n_exceed int64 [P], agree bool [P]) on
+    threshold_series() at window W_; the float64 reference gets the threshold float32 holds."""
+    import oracle
+    key = ("ref", W_, thr)
+    if key not in _thr_cache:
+        x = threshold_series()
+        twin = oracle.c_rolling_score(x, W_, thr)
+        n64 = oracle.rolling_score_f64(x, W_, float(np.float32(thr)))[2]
+        _thr_cache[key] = (twin, n64, twin["n_exceed"] == n64)
+    return _thr_cache[key]
+
+
+THR_STREAM_PODS = THR_SHAPE[0]  # pods of the series the streaming-timeline reference walks: all of them
+
+
+def threshold_stream_ref(thr, H):
+    """tests/stream_timeline_ref.py over the first THR_STREAM_PODS pods of the dyadic threshold series
+    in THR_STREAM_WINDOWS at W = 60, gap 3, min_count 3: the six outputs after every window."""
+    import stream_timeline_ref as SR
+    key = ("stream", thr, H)
+    if key not in _thr_cache:
+        x = threshold_series(dyadic=True)[:, :THR_STREAM_PODS]
+        _thr_cache[key] = SR.stream_timeline(x, THR_SHAPE[3], thr, 3, 3, H, THR_STREAM_WINDOWS)
+    return _thr_cache[key]
+
+
+# ---- follower clamp of krca_rca_first_mover_key --------------------------------------------------
+CLAMP = (1 << 20) - 1
+FOLLOWERS = (0, 1, CLAMP - 1, CLAMP, CLAMP + 1, CLAMP + 6, 2 ** 31 - 1)
+# (caller_later, caller_concurrent): each count alone in either place, then sums that cross the clamp
+# while both addends stay below it, and a sum that leaves int32
+FOLLOWER_PAIRS = tuple((f, 0) for f in FOLLOWERS) + tuple((0, f) for f in FOLLOWERS[1:]) + (
+    (1 << 19, (1 << 19) - 2), (1 << 19, (1 << 19) - 1), (1 << 19, 1 << 19), (CLAMP - 1, 1), (CLAMP, CLAMP), (1, CLAMP - 1),
+    (2 ** 31 - 1, 2 ** 31 - 1))
+DENORMAL = float(np.float32(2.0 ** -149))
+KEY_PEAKS = (0.0, DENORMAL, 1.5, float("inf"))  # include/krca.h: peak >= 0
+
+
+def first_mover_key_case():
+    """Fabricated inputs of krca_rca_first_mover_key, the cross product of FOLLOWER_PAIRS, dep_earlier
+    in {0, 1}, onset in {-1, 0, 5} and KEY_PEAKS -> (onset int32, peak float32, prec dict of int32)."""
+    rows = [(on, pk, de, cl, cc) for cl, cc in FOLLOWER_PAIRS for de in (0, 1) for on in (-1, 0, 5) for pk in KEY_PEAKS]
+    on, pk, de, cl, cc = (np.array(c) for c in zip(*rows))
+    prec = dict(dep_earlier=de.astype(np.int32), caller_later=cl.astype(np.int32), caller_concurrent=cc.astype(np.int32))
+    return on.astype(np.int32), pk.astype(np.float32), prec
