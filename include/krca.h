@@ -123,6 +123,34 @@ int krca_rolling_timeline(const float* x, int64_t P, int32_t M, int32_t T, int32
                           int32_t* onset /*[P]*/, int32_t* last /*[P]*/, int32_t* count /*[P]*/, float* peak /*[P]*/,
                           int8_t* lead /*[P]*/, uint8_t* n_metrics /*[P]*/, void* stream);
 
+/* ---- a5s: level-shift score -- a sustained change of level against a robust baseline (new
+ * primitive; stands beside krca_rolling_score, whose last-step z cannot see a fault that began
+ * inside its own window).  x as krca_rolling_score reads it.  Per series s = p*M + m:
+ *   baseline = the B samples at t in [T-R-G-B, T-R-G), recent = the R samples at t in [T-R, T);
+ *   the G guard rows between them are not read.
+ *   Order: the total order of the key k(x) = (bits & 0x80000000) ? ~bits : bits | 0x80000000,
+ *   compared unsigned: -0 < +0, a positive-sign NaN above +Inf, a negative-sign NaN below -Inf.
+ *   lmed(n values) = the element of 0-based rank (n-1)/2 in that order, with its own bits.
+ *   base_med = lmed(baseline);  base_mad = lmed(fabsf(x_i - base_med)) over the baseline (float32
+ *   subtraction, one rounding);  recent_med = lmed(recent);
+ *   den = 1.4826 * (double)base_mad;  if (!(den > (double)min_scale)) den = min_scale;
+ *   shift = den > 0 ? (float)(((double)recent_med - (double)base_med) / den) : 0.0f  (signed).
+ * Per pod: score[p] = max over m of fabsf(shift) skipping NaN (all NaN: 0); lead[p] = the lowest m
+ * that attains it when score > 0, else -1.
+ * KRCA_EINVAL before any device work (nothing written): M no power of two <= 64, B outside
+ * [2, krca_shift_max_baseline()], R outside [1, krca_shift_max_recent()], G < 0, B + G + R > T,
+ * min_scale not finite or < 0, P < 0 or P*M >= 2^32.  P == 0 is a no-op success.
+ * Samples are expected finite; a NaN / Inf never faults and gives NaN where tests/shift_ref.py gives
+ * NaN and the same bits elsewhere.
+ * Buffers: shift / base_med / base_mad / recent_med [P][M] and score / lead [P] are fully written, no
+ * initialisation needed; no workspace; one kernel, no memset (safe for graph capture). */
+int32_t krca_shift_max_baseline(void); /* 256 */
+int32_t krca_shift_max_recent(void);   /* 64 */
+int krca_shift_score(const float* x, int64_t P, int32_t M, int32_t T, int32_t B, int32_t R, int32_t G,
+                     float min_scale,
+                     float* shift /*[P][M]*/, float* base_med /*[P][M]*/, float* base_mad /*[P][M]*/,
+                     float* recent_med /*[P][M]*/, float* score /*[P]*/, int8_t* lead /*[P]*/, void* stream);
+
 /* Onset precedence over the pull-CSR (row k = the callers j of k, edges j -> k), single device, whole
  * graph; onset as krca_rolling_timeline writes it (< 0: none).  An edge j -> k with j != k,
  * onset_j >= 0 and onset_k >= 0 is classified, with slack >= 0:  k EARLIER than j when

@@ -23,7 +23,8 @@ from .traces import TracesAgent
 
 class Coordinator:
     def __init__(self, k8s_client, engine=None, rank_config=None, correlations=False, corr_channel=0, corr_span=None,
-                 corr_max_lag=8, corr_tau=0.5, corr_slack=0, blast_radius=False, blast_bins=16):
+                 corr_max_lag=8, corr_tau=0.5, corr_slack=0, blast_radius=False, blast_bins=16, level_shifts=False,
+                 **shift_options):
         from krca.rca import RANKING
         self.k8s_client = k8s_client
         self._engine = engine
@@ -38,8 +39,13 @@ class Coordinator:
         self.blast_radius = bool(blast_radius)
         self.blast_bins = int(blast_bins)
         self._rank_ctx = None
+        # level_shifts=True: the metrics agent also scores level shifts (its "level_shifts" key; shift_*
+        # options are passed through to it) and the comprehensive result gains the additive key
+        # "level_shift_root_causes": the same ranking seeded with the shift score
+        self.level_shifts = bool(level_shifts)
         self.metrics_agent = MetricsAgent(k8s_client, engine, window=self.rank_config.window,
-                                          z_threshold=self.rank_config.z_threshold)
+                                          z_threshold=self.rank_config.z_threshold, level_shift=self.level_shifts,
+                                          **shift_options)
         self.logs_agent = LogsAgent(k8s_client, engine)
         self.traces_agent = TracesAgent(k8s_client, engine)
         self.topology_agent = TopologyAgent(k8s_client, engine)
@@ -86,6 +92,10 @@ class Coordinator:
             out['ranked_root_causes'] = ranked
         if self.blast_radius and ranked:
             out['blast_radius'] = self._blast_radius()
+        if self.level_shifts:
+            shifted = self._rank_level_shifts(namespace)
+            if shifted is not None:
+                out['level_shift_root_causes'] = shifted
         if self.correlations:
             corr = self._correlations(namespace, ranked)
             if corr is not None:
@@ -173,6 +183,21 @@ class Coordinator:
         br = self.engine.blast_radius(x['row_ptr'], x['col'], x['idx'], pull=True, direction='dependents',
                                       bins=self.blast_bins, **x['mark'])
         return br.summary(names=[x['prefix'] + n for n in x['names']])
+
+    # -- additive level-shift ranking ------------------------------------
+    def _rank_level_shifts(self, namespace):
+        """The rows of _rank_root_causes with the level-shift score as the seed ('anomaly' is that
+        score); None without the bulk accessors or when the history is too short to score."""
+        c = self.k8s_client
+        sh = self.metrics_agent.last_shift
+        if sh is None or not hasattr(c, 'get_dependency_csr'):
+            return None
+        names, row_ptr, col, outdeg = c.get_dependency_csr(namespace)
+        idx, val, rank = self.engine.rank_root_causes(sh['score'], row_ptr, col, outdeg, self.rank_config,
+                                                      n_metrics=int(sh['shift'].shape[1]))
+        sc = sh['score_host']
+        return [{'component': f"Pod/{names[i]}", 'rank': r + 1, 'score': float(v), 'pagerank': float(rank[i]),
+                 'anomaly': float(sc[i])} for r, (i, v) in enumerate(zip(idx.tolist(), val.tolist()))]
 
     # -- additive ranking ----------------------------------------------------------------
     def _rank_root_causes(self, namespace):

@@ -39,7 +39,8 @@ def to_f32_threshold_safe(values):
 
 class MetricsAgent(BaseAgent):
     def __init__(self, k8s_client, engine=None, window=60, z_threshold=3.0, anomaly_topk=10, timeline=False,
-                 timeline_gap=3, timeline_min_count=3):
+                 timeline_gap=3, timeline_min_count=3, level_shift=False, shift_baseline=120, shift_recent=3,
+                 shift_guard=0, shift_min_scale=0.0, shift_threshold=None):
         super().__init__(k8s_client, engine)
         self.window = window
         self.z_threshold = z_threshold
@@ -49,21 +50,35 @@ class MetricsAgent(BaseAgent):
         self.timeline = bool(timeline)
         self.timeline_gap = timeline_gap
         self.timeline_min_count = timeline_min_count
+        # level_shift=True: the bulk path also runs krca_shift_score (the median of the last shift_recent
+        # samples against the median / MAD of the shift_baseline samples before them and a guard) and the
+        # result gains the additive key "level_shifts": the sustained changes of level, which the
+        # last-step z-score above cannot see
+        self.level_shift = bool(level_shift)
+        self.shift_baseline = int(shift_baseline)
+        self.shift_recent = int(shift_recent)
+        self.shift_guard = int(shift_guard)
+        self.shift_min_scale = float(shift_min_scale)
+        self.shift_threshold = shift_threshold  # None: max(z_threshold, rca.null_floor(P*M))
         self.last_scores = None  # device outputs of the last bulk run (used by the Coordinator)
+        self.last_shift = None   # outputs of the last krca_shift_score run (level_shift=True)
 
     # ------------------------------------------------------------------------------------
     def analyze(self, namespace, context=None, **kwargs):
         self.reset()
         self.last_scores = None
+        self.last_shift = None
         try:
             self._maybe_set_context(context)
             bulk = getattr(self.k8s_client, "get_pod_metric_tensor", None)
-            anomalies = timeline = None
+            anomalies = timeline = shifts = None
             if bulk is not None:
                 names, x = bulk(namespace)
                 pods, flags, anomalies = self._score_tensor(names, x)
                 if self.timeline and self.last_scores is not None:
                     timeline = self._anomaly_timeline(names, anomalies, self.last_scores)
+                if self.level_shift:
+                    shifts = self._level_shifts(names, x)
             else:
                 pod_metrics = self.k8s_client.get_pod_metrics(namespace)
                 pods, flags = self._score_dict(pod_metrics)
@@ -78,6 +93,8 @@ class MetricsAgent(BaseAgent):
                 res["anomalies"] = anomalies
             if timeline is not None:
                 res["anomaly_timeline"] = timeline
+            if shifts is not None:
+                res["level_shifts"] = shifts
             return res
         except Exception as e:  # ref:agents/metrics_agent.py:58-67
             return self._error_result("metrics", e)
@@ -142,6 +159,48 @@ class MetricsAgent(BaseAgent):
             rows.append({"resource": a["resource"], "onset_step": int(out["onset_host"][p]),
                          "last_step": int(out["last_host"][p]), "episode_count": int(out["count_host"][p]),
                          "lead_metric": int(out["lead_host"][p]), "n_metrics": int(out["n_metrics_host"][p])})
+        return rows
+
+    def _level_shifts(self, names, x):
+        """The top anomaly_topk pods by level-shift score above the threshold, in rank order: the lead
+        metric's signed shift with its baseline median, recent median and scale."""
+        T, P, M = x.shape
+        B, R, G = self.shift_baseline, self.shift_recent, self.shift_guard
+        if P == 0:
+            return []
+        if T < B + G + R:
+            self.add_reasoning_step(
+                observation=f"Metric history of {T} steps is shorter than the level-shift windows "
+                            f"({B} baseline + {G} guard + {R} recent)",
+                conclusion="Unable to score level shifts")
+            return []
+        from krca.rca import null_floor
+        out = self.engine.shift_score(x, baseline=B, recent=R, guard=G, min_scale=self.shift_min_scale)
+        self.last_shift = out
+        thr = (float(self.shift_threshold) if self.shift_threshold is not None
+               else max(float(self.z_threshold), null_floor(P * M)))
+        rows = []
+        idx, val = self.engine.topk(out["score"], min(self.anomaly_topk, P))
+        for p, s in zip(idx.tolist(), val.tolist()):
+            if not s > thr:
+                break
+            m = int(out["lead_host"][p])
+            med, mad, rec = (float(out[k][p, m]) for k in ("base_med_host", "base_mad_host", "recent_med_host"))
+            den, floor = 1.4826 * mad, float(np.float32(self.shift_min_scale))  # krca_shift_score's scale
+            if not den > floor:
+                den = floor
+            rows.append({
+                "resource": f"Pod/{names[p]}",
+                "metric": m,
+                "shift": float(out["shift_host"][p, m]),
+                "baseline": med,
+                "recent": rec,
+                "scale": float(den),
+                "description": (f"Level shift of {float(out['shift_host'][p, m]):+.2f} robust deviations in metric {m}: "
+                                f"median {rec:.2f} over the last {R} steps against {med:.2f} over the "
+                                f"{B} steps before them"),
+                "severity": "high" if s > 2 * thr else "medium",
+            })
         return rows
 
     # -- shared reporting (ref:agents/metrics_agent.py:69-161) ---------------------------

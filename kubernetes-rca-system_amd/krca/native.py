@@ -30,6 +30,10 @@ SIGNATURES = {
     "krca_rolling_score": (c_i32, [c_vp, c_i64, c_i32, c_i32, c_i32, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "krca_rolling_timeline": (c_i32, [c_vp, c_i64, c_i32, c_i32, c_i32, c_f32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp,
                                       c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "krca_shift_max_baseline": (c_i32, []),
+    "krca_shift_max_recent": (c_i32, []),
+    "krca_shift_score": (c_i32, [c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                 c_vp, c_vp]),
     "krca_rca_precede_ws_size": (c_i64, [c_i64]),
     "krca_rca_precede": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "krca_rca_first_mover_key": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp]),
@@ -414,6 +418,39 @@ class NativeEngine:
         for key in self.TIMELINE_KEYS:
             res[key + "_host"] = d[key].cpu().numpy()
         res["gap"], res["min_count"] = int(gap), int(min_count)
+        return res
+
+    # -- a5s: level-shift score (include/krca.h, csrc/shift.hip) -------------------------------------
+    SHIFT_KEYS = ("shift", "base_med", "base_mad", "recent_med", "score", "lead")
+
+    def shift_score_device(self, x, baseline=120, recent=3, guard=0, min_scale=0.0, out=None):
+        """Launch only (no sync): x float32 [T, P, M] on the device -> dict of device tensors shift,
+        base_med, base_mad, recent_med float32 [P, M], score float32 [P], lead int8 [P]
+        (krca_shift_score)."""
+        torch = self.torch
+        T, P, M = x.shape
+        new = lambda dt, *shape: torch.empty(shape, dtype=dt, device=self.device)  # noqa: E731
+        if out is None:
+            out = dict(shift=new(torch.float32, P, M), base_med=new(torch.float32, P, M),
+                       base_mad=new(torch.float32, P, M), recent_med=new(torch.float32, P, M),
+                       score=new(torch.float32, P), lead=new(torch.int8, P))
+        _check(self.lib.krca_shift_score(self.ptr(x), P, M, T, int(baseline), int(recent), int(guard),
+                                         float(min_scale), self.ptr(out["shift"]), self.ptr(out["base_med"]),
+                                         self.ptr(out["base_mad"]), self.ptr(out["recent_med"]),
+                                         self.ptr(out["score"]), self.ptr(out["lead"]), self._stream()),
+               "krca_shift_score")
+        return out
+
+    def shift_score(self, x, baseline=120, recent=3, guard=0, min_scale=0.0):
+        """shift_score_device's dict (device tensors) plus host copies under '<key>_host' and the
+        window arguments."""
+        x = self._dev(x, self.torch.float32)
+        d = self.shift_score_device(x, baseline, recent, guard, min_scale)
+        res = dict(d)
+        for key in self.SHIFT_KEYS:
+            res[key + "_host"] = d[key].cpu().numpy()
+        res["baseline"], res["recent"], res["guard"], res["min_scale"] = (int(baseline), int(recent), int(guard),
+                                                                          float(min_scale))
         return res
 
     def rca_precede_device(self, onset, row_ptr, col, slack=0):
