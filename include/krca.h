@@ -151,6 +151,38 @@ int krca_shift_score(const float* x, int64_t P, int32_t M, int32_t T, int32_t B,
                      float* shift /*[P][M]*/, float* base_med /*[P][M]*/, float* base_mad /*[P][M]*/,
                      float* recent_med /*[P][M]*/, float* score /*[P]*/, int8_t* lead /*[P]*/, void* stream);
 
+/* ---- a5p: peer deviation score -- a pod against the other members of its group now (its replicas, the
+ * pods of its node, the other nodes), not against its own past (new primitive; stands beside
+ * krca_shift_score and reuses its order, lmed and scale).  v [P][M] is any per-pod statistic, usually
+ * krca_shift_score's shift or recent_med.  Group g's members are member[grp_ptr[g] .. grp_ptr[g+1]); an id
+ * outside [0, P) is ignored as if it were not listed; a pod listed twice, or in two groups, has
+ * unspecified values but causes no out-of-bounds access.  Per (g, m) over the n valid members:
+ *   grp_med = lmed(v);  grp_mad = lmed(fabsf(v_i - grp_med)) (float32 subtraction);  n == 0: both 0;
+ *   den = 1.4826 * (double)grp_mad;  if (!(den > (double)min_scale)) den = min_scale;
+ *   peer[p][m] = den > 0 ? (float)(((double)v - (double)grp_med) / den) : 0.0f;
+ *   n < min_members: the medians are still written, the members' peer is 0 and grp_out is 0;
+ *   grp_out = the number of members with fabsf(peer) > out_thr (a NaN does not count).
+ * Per pod: score[p] = max over m of fabsf(peer) skipping NaN; lead[p] = the lowest m that attains it, or -1
+ * when the score is 0.  A pod in no group: peer 0, score 0, lead -1.
+ * KRCA_EINVAL before any device work (nothing written): M no power of two <= 64, min_members < 1, min_scale
+ * or out_thr negative or not finite, P, G or n_member negative, P*M >= 2^32, G >= 2^32.  G == 0 is valid
+ * (every pod gets the defaults); P == 0 is a no-op success.
+ * Buffers: peer [P][M], score / lead [P], grp_med / grp_mad / grp_out [G][M] are fully written, no
+ * initialisation needed; ws = krca_peer_ws_size(P, M, G, n_member) bytes, initialised by the call; no
+ * memset by the caller, no device-to-host sync, no allocation (safe for graph capture); every output is
+ * deterministic.  Groups of up to krca_peer_small_max() members take one wave each, up to
+ * krca_peer_lds_cap() an LDS tile, larger ones the workspace (csrc/peer.hip). */
+int32_t krca_peer_small_max(void); /* 64 */
+int32_t krca_peer_lds_cap(void);   /* 4096 */
+int64_t krca_peer_ws_size(int64_t P, int32_t M, int64_t G, int64_t n_member);
+int krca_peer_score(const float* v /*[P][M]*/, int64_t P, int32_t M,
+                    const int64_t* grp_ptr /*[G+1]*/, const int32_t* member /*[n_member]*/,
+                    int64_t G, int64_t n_member,
+                    int32_t min_members, float min_scale, float out_thr,
+                    float* peer /*[P][M]*/, float* score /*[P]*/, int8_t* lead /*[P]*/,
+                    float* grp_med /*[G][M]*/, float* grp_mad /*[G][M]*/, int32_t* grp_out /*[G][M]*/,
+                    void* ws, void* stream);
+
 /* Onset precedence over the pull-CSR (row k = the callers j of k, edges j -> k), single device, whole
  * graph; onset as krca_rolling_timeline writes it (< 0: none).  An edge j -> k with j != k,
  * onset_j >= 0 and onset_k >= 0 is classified, with slack >= 0:  k EARLIER than j when

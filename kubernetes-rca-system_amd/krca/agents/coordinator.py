@@ -24,7 +24,7 @@ from .traces import TracesAgent
 class Coordinator:
     def __init__(self, k8s_client, engine=None, rank_config=None, correlations=False, corr_channel=0, corr_span=None,
                  corr_max_lag=8, corr_tau=0.5, corr_slack=0, blast_radius=False, blast_bins=16, level_shifts=False,
-                 **shift_options):
+                 peer_deviations=False, **shift_options):
         from krca.rca import RANKING
         self.k8s_client = k8s_client
         self._engine = engine
@@ -43,9 +43,14 @@ class Coordinator:
         # options are passed through to it) and the comprehensive result gains the additive key
         # "level_shift_root_causes": the same ranking seeded with the shift score
         self.level_shifts = bool(level_shifts)
+        # peer_deviations=True: the metrics agent also scores pods against their replicas and nodes against
+        # nodes (its "peer_deviations" / "service_wide" / "node_deviations" keys; peer_* options and
+        # node_threshold are passed through) and the comprehensive result gains the additive keys
+        # "peer_root_causes" (the same ranking seeded with the peer score) and "node_deviations" 
+        self.peer_deviations = bool(peer_deviations)
         self.metrics_agent = MetricsAgent(k8s_client, engine, window=self.rank_config.window,
                                           z_threshold=self.rank_config.z_threshold, level_shift=self.level_shifts,
-                                          **shift_options)
+                                          peer_deviation=self.peer_deviations, **shift_options)
         self.logs_agent = LogsAgent(k8s_client, engine)
         self.traces_agent = TracesAgent(k8s_client, engine)
         self.topology_agent = TopologyAgent(k8s_client, engine)
@@ -96,6 +101,12 @@ class Coordinator:
             shifted = self._rank_level_shifts(namespace)
             if shifted is not None:
                 out['level_shift_root_causes'] = shifted
+        if self.peer_deviations:
+            peered = self._rank_peer_deviations(namespace)
+            if peered is not None:
+                out['peer_root_causes'] = peered
+            if 'node_deviations' in results['metrics']:
+                out['node_deviations'] = results['metrics']['node_deviations']
         if self.correlations:
             corr = self._correlations(namespace, ranked)
             if corr is not None:
@@ -196,6 +207,22 @@ class Coordinator:
         idx, val, rank = self.engine.rank_root_causes(sh['score'], row_ptr, col, outdeg, self.rank_config,
                                                       n_metrics=int(sh['shift'].shape[1]))
         sc = sh['score_host']
+        return [{'component': f"Pod/{names[i]}", 'rank': r + 1, 'score': float(v), 'pagerank': float(rank[i]),
+                 'anomaly': float(sc[i])} for r, (i, v) in enumerate(zip(idx.tolist(), val.tolist()))]
+
+    # -- additive peer-deviation ranking --------------------------------
+    def _rank_peer_deviations(self, namespace):
+        """The rows of _rank_root_causes with the peer deviation score as the seed ('anomaly' is that
+        score); None without the bulk accessors or when nothing was scored."""
+        c = self.k8s_client
+        pr = self.metrics_agent.last_peer
+        if pr is None or not hasattr(c, 'get_dependency_csr'):
+            return None
+        names, row_ptr, col, outdeg = c.get_dependency_csr(namespace)
+        out = pr['service']
+        idx, val, rank = self.engine.rank_root_causes(out['score'], row_ptr, col, outdeg, self.rank_config,
+                                                      n_metrics=int(out['peer'].shape[1]))
+        sc = out['score_host']
         return [{'component': f"Pod/{names[i]}", 'rank': r + 1, 'score': float(v), 'pagerank': float(rank[i]),
                  'anomaly': float(sc[i])} for r, (i, v) in enumerate(zip(idx.tolist(), val.tolist()))]
 

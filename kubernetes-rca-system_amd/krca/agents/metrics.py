@@ -19,6 +19,11 @@ import numpy as np
 from .base import BaseAgent
 
 CPU_CH, MEM_CH = 0, 1
+# peer deviation defaults per peer_value: (scale floor, pod threshold), and the node threshold.  Each
+# threshold is 4 % above the largest null maximum measured on clean synth.make_metrics_replicas data at C2
+# size with the NumPy restatement (the table of DESIGN.md §3.20)
+PEER_DEFAULTS = {"shift": (0.5, 6.5), "level": (1.0, 7.6)}
+NODE_THRESHOLD = 7.0
 # flag bits produced by the device kernels (include/krca.h)
 F_CPU80, F_CPU90, F_MEM80, F_MEM90 = 1, 2, 4, 8
 
@@ -40,7 +45,8 @@ def to_f32_threshold_safe(values):
 class MetricsAgent(BaseAgent):
     def __init__(self, k8s_client, engine=None, window=60, z_threshold=3.0, anomaly_topk=10, timeline=False,
                  timeline_gap=3, timeline_min_count=3, level_shift=False, shift_baseline=120, shift_recent=3,
-                 shift_guard=0, shift_min_scale=0.0, shift_threshold=None):
+                 shift_guard=0, shift_min_scale=0.0, shift_threshold=None, peer_deviation=False, peer_value="shift",
+                 peer_min_members=4, peer_min_scale=None, peer_threshold=None, node_threshold=None):
         super().__init__(k8s_client, engine)
         self.window = window
         self.z_threshold = z_threshold
@@ -62,16 +68,30 @@ class MetricsAgent(BaseAgent):
         self.shift_threshold = shift_threshold  # None: max(z_threshold, rca.null_floor(P*M))
         self.last_scores = None  # device outputs of the last bulk run (used by the Coordinator)
         self.last_shift = None   # outputs of the last krca_shift_score run (level_shift=True)
+        # peer_deviation=True: the bulk path also scores each pod against its replicas now, not against its
+        # own past (krca_peer_score over the shift statistics, grouped by the client's get_pod_groups
+        # labels), then the nodes against each other; the result gains the additive keys
+        # "peer_deviations", "service_wide" and "node_deviations" 
+        if peer_value not in PEER_DEFAULTS:
+            raise ValueError(f"peer_value must be one of {sorted(PEER_DEFAULTS)}")
+        self.peer_deviation = bool(peer_deviation)
+        self.peer_value = peer_value
+        self.peer_min_members = int(peer_min_members)
+        self.peer_min_scale = peer_min_scale    # None: PEER_DEFAULTS[peer_value][0]
+        self.peer_threshold = peer_threshold    # None: PEER_DEFAULTS[peer_value][1]
+        self.node_threshold = node_threshold    # None: NODE_THRESHOLD
+        self.last_peer = None    # outputs of the last peer-deviation run (peer_deviation=True)
 
     # ------------------------------------------------------------------------------------
     def analyze(self, namespace, context=None, **kwargs):
         self.reset()
         self.last_scores = None
         self.last_shift = None
+        self.last_peer = None
         try:
             self._maybe_set_context(context)
             bulk = getattr(self.k8s_client, "get_pod_metric_tensor", None)
-            anomalies = timeline = shifts = None
+            anomalies = timeline = shifts = peers = None
             if bulk is not None:
                 names, x = bulk(namespace)
                 pods, flags, anomalies = self._score_tensor(names, x)
@@ -79,6 +99,8 @@ class MetricsAgent(BaseAgent):
                     timeline = self._anomaly_timeline(names, anomalies, self.last_scores)
                 if self.level_shift:
                     shifts = self._level_shifts(names, x)
+                if self.peer_deviation:
+                    peers = self._peer_deviations(namespace, names, x)
             else:
                 pod_metrics = self.k8s_client.get_pod_metrics(namespace)
                 pods, flags = self._score_dict(pod_metrics)
@@ -95,6 +117,8 @@ class MetricsAgent(BaseAgent):
                 res["anomaly_timeline"] = timeline
             if shifts is not None:
                 res["level_shifts"] = shifts
+            if peers is not None:
+                res.update(peers)
             return res
         except Exception as e:  # ref:agents/metrics_agent.py:58-67
             return self._error_result("metrics", e)
@@ -202,6 +226,107 @@ class MetricsAgent(BaseAgent):
                 "severity": "high" if s > 2 * thr else "medium",
             })
         return rows
+
+    def _peer_deviations(self, namespace, names, x):
+        """{"peer_deviations", "service_wide", "node_deviations"}: the top anomaly_topk pods whose deviation
+        from their replicas exceeds the threshold, in rank order; the services whose own median shift exceeds
+        the level-shift threshold (the whole service moved, not a pod); the nodes whose pods deviate from
+        their replicas together, against the other nodes."""
+        from krca.peers import PeerGroups, node_effects
+        from krca.rca import null_floor
+        res = {"peer_deviations": [], "service_wide": [], "node_deviations": []}
+        T, P, M = x.shape
+        B, R, G = self.shift_baseline, self.shift_recent, self.shift_guard
+        if P == 0:
+            return res
+        getter = getattr(self.k8s_client, "get_pod_groups", None)
+        labels = (getter(namespace) or {}) if getter is not None else {}
+        if labels.get("service") is None:
+            self.add_reasoning_step(
+                observation="The client serves no service labels for its pods (get_pod_groups)",
+                conclusion="Unable to score peer deviations")
+            return res
+        if T < B + G + R:
+            self.add_reasoning_step(
+                observation=f"Metric history of {T} steps is shorter than the level-shift windows "
+                            f"({B} baseline + {G} guard + {R} recent)",
+                conclusion="Unable to score peer deviations")
+            return res
+        sh = self.last_shift
+        if sh is None:
+            sh = self.engine.shift_score(x, baseline=B, recent=R, guard=G, min_scale=self.shift_min_scale)
+        floor, thr = PEER_DEFAULTS[self.peer_value]
+        floor = float(floor if self.peer_min_scale is None else self.peer_min_scale)
+        thr = float(thr if self.peer_threshold is None else self.peer_threshold)
+        node_thr = float(NODE_THRESHOLD if self.node_threshold is None else self.node_threshold)
+        shift_thr = (float(self.shift_threshold) if self.shift_threshold is not None
+                     else max(float(self.z_threshold), null_floor(P * M)))
+        services = PeerGroups.from_labels(self.engine, labels["service"])
+        args = dict(min_members=self.peer_min_members, min_scale=floor, out_thr=thr)
+        out = self.engine.peer_score(sh["shift" if self.peer_value == "shift" else "recent_med"], services, **args)
+        own = out if self.peer_value == "shift" else self.engine.peer_score(sh["shift"], services, **args)
+        self.last_peer = {"value": self.peer_value, "shift": sh, "service": out, "service_shift": own, "nodes": None,
+                          "min_scale": floor, "threshold": thr, "node_threshold": node_thr}
+        group_of, size = services.group_of(), services.sizes()
+        idx, val = self.engine.topk(out["score"], min(self.anomaly_topk, P))
+        for p, s in zip(idx.tolist(), val.tolist()):
+            if not s > thr:
+                break
+            m, g = int(out["lead_host"][p]), int(group_of[p])
+            med, mad = float(out["grp_med_host"][g, m]), float(out["grp_mad_host"][g, m])
+            dev = float(out["peer_host"][p, m])
+            den = 1.4826 * mad
+            if not den > float(np.float32(floor)):
+                den = float(np.float32(floor))
+            others = int(out["grp_out_host"][g, m]) - 1
+            res["peer_deviations"].append({
+                "resource": f"Pod/{names[p]}",
+                "service": g,
+                "metric": m,
+                "deviation": dev,
+                "group_median": med,
+                "scale": float(den),
+                "peers_out": others,
+                "group_size": int(size[g]),
+                "description": (f"Metric {m} deviates {dev:+.2f} robust deviations from the {int(size[g]) - 1} other "
+                                f"replicas of service group {g} ({others} of them are out as well)"),
+                "severity": "high" if s > 2 * thr else "medium",
+            })
+        gm = np.where(np.isnan(own["grp_med_host"]), np.float32(0), np.abs(own["grp_med_host"]))
+        moved = gm.max(axis=1) if gm.shape[0] else np.zeros(0, np.float32)
+        for g in sorted(np.flatnonzero((moved > shift_thr) & (size >= self.peer_min_members)).tolist(),
+                        key=lambda g: (-float(moved[g]), g)):
+            m = int(gm[g].argmax())
+            res["service_wide"].append({
+                "service": g,
+                "metric": m,
+                "shift": float(own["grp_med_host"][g, m]),
+                "members": int(size[g]),
+                "description": (f"The whole of service group {g} moved: the median level shift of its {int(size[g])} "
+                                f"replicas in metric {m} is {float(own['grp_med_host'][g, m]):+.2f} robust deviations"),
+            })
+        if labels.get("node") is not None:
+            nodes = PeerGroups.from_labels(self.engine, labels["node"])
+            ne = node_effects(self.engine, out["peer"], services, nodes, min_members=self.peer_min_members, out_thr=thr)
+            self.last_peer["nodes"] = ne
+            order = sorted(range(nodes.n_groups), key=lambda n: (-float(ne["score"][n]), n))[:self.anomaly_topk]
+            for n in order:
+                s = float(ne["score"][n])
+                if not s > node_thr:
+                    break
+                m = int(ne["lead"][n])
+                res["node_deviations"].append({
+                    "node": n,
+                    "metric": m,
+                    "deviation": float(ne["deviation"][n, m]),
+                    "effect": float(ne["effect"][n, m]),
+                    "pods": int(ne["pods"][n]),
+                    "description": (f"The {int(ne['pods'][n])} pods of node {n} deviate from their replicas together: "
+                                    f"metric {m} by a median of {float(ne['effect'][n, m]):+.2f}, "
+                                    f"{float(ne['deviation'][n, m]):+.2f} robust deviations from the other nodes"),
+                    "severity": "high" if s > 2 * node_thr else "medium",
+                })
+        return res
 
     # -- shared reporting (ref:agents/metrics_agent.py:69-161) ---------------------------
     def _report_usage(self, pods, flags, label, key, ch, f80, f90):

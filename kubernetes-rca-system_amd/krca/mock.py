@@ -188,10 +188,16 @@ class MeshClient(MockK8sClient):
     comprehensive run scores the mesh and ranks its pods; the dict methods keep serving the C1
     objects.  Used to check that ``ranked_root_causes`` equals the bench / RcaStep ranking."""
 
-    def __init__(self, mesh, x, names=None, **kw):
+    def __init__(self, mesh, x, names=None, groups=None, **kw):
         super().__init__(**kw)
         self.mesh, self.x = mesh, x
         self._mesh_names = names
+        self._groups = groups
+
+    def get_pod_groups(self, namespace):
+        """Optional bulk accessor: {"service": int32 [P], "node": int32 [P]} labels in the tensor's pod
+        order (a label < 0: none); either entry may be missing."""
+        return dict(self._groups or {})
 
     def get_pod_metric_tensor(self, namespace):
         return (self._mesh_names or self.mesh.names()), self.x

@@ -34,6 +34,11 @@ SIGNATURES = {
     "krca_shift_max_recent": (c_i32, []),
     "krca_shift_score": (c_i32, [c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp,
                                  c_vp, c_vp]),
+    "krca_peer_small_max": (c_i32, []),
+    "krca_peer_lds_cap": (c_i32, []),
+    "krca_peer_ws_size": (c_i64, [c_i64, c_i32, c_i64, c_i64]),
+    "krca_peer_score": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp, c_i64, c_i64, c_i32, c_f32, c_f32, c_vp, c_vp, c_vp,
+                                c_vp, c_vp, c_vp, c_vp, c_vp]),
     "krca_rca_precede_ws_size": (c_i64, [c_i64]),
     "krca_rca_precede": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "krca_rca_first_mover_key": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp]),
@@ -451,6 +456,52 @@ class NativeEngine:
             res[key + "_host"] = d[key].cpu().numpy()
         res["baseline"], res["recent"], res["guard"], res["min_scale"] = (int(baseline), int(recent), int(guard),
                                                                           float(min_scale))
+        return res
+
+    # -- a5p: peer deviation score (include/krca.h, csrc/peer.hip) ------------------------------------
+    PEER_KEYS = ("peer", "score", "lead", "grp_med", "grp_mad", "grp_out")
+
+    def _peer_groups(self, groups):
+        """krca.peers.PeerGroups, or a (grp_ptr, member) pair of host / device arrays -> device tensors
+        (grp_ptr int64 [G + 1], member int32 [n_member]), G, n_member."""
+        gp, mem = (groups.grp_ptr, groups.member) if hasattr(groups, "grp_ptr") else groups
+        if not isinstance(gp, self.torch.Tensor):
+            gp = np.ascontiguousarray(gp, np.int64)
+        if not isinstance(mem, self.torch.Tensor):
+            mem = np.ascontiguousarray(mem, np.int32)
+        gp, mem = self._dev(gp, self.torch.int64), self._dev(mem, self.torch.int32)
+        return gp, mem, int(gp.numel()) - 1, int(mem.numel())
+
+    def peer_score_device(self, v, groups, min_members=4, min_scale=0.0, out_thr=3.0, out=None):
+        """Launch only (no sync): v float32 [P, M] on the device, groups a krca.peers.PeerGroups or a
+        (grp_ptr, member) pair -> dict of device tensors peer float32 [P, M], score float32 [P], lead
+        int8 [P], grp_med / grp_mad float32 [G, M], grp_out int32 [G, M] (krca_peer_score)."""
+        torch = self.torch
+        P, M = v.shape
+        gp, mem, G, n_member = self._peer_groups(groups)
+        if G < 0:
+            raise KrcaError("peer_score: grp_ptr needs at least one element")
+        new = lambda dt, *shape: torch.empty(shape, dtype=dt, device=self.device)  # noqa: E731
+        if out is None:
+            out = dict(peer=new(torch.float32, P, M), score=new(torch.float32, P), lead=new(torch.int8, P),
+                       grp_med=new(torch.float32, G, M), grp_mad=new(torch.float32, G, M),
+                       grp_out=new(torch.int32, G, M))
+        ws = self._workspace("peer_score", self.lib.krca_peer_ws_size(P, M, G, n_member))
+        _check(self.lib.krca_peer_score(self.ptr(v), P, M, self.ptr(gp), self.ptr(mem), G, n_member, int(min_members),
+                                        float(min_scale), float(out_thr), self.ptr(out["peer"]), self.ptr(out["score"]),
+                                        self.ptr(out["lead"]), self.ptr(out["grp_med"]), self.ptr(out["grp_mad"]),
+                                        self.ptr(out["grp_out"]), self.ptr(ws), self._stream()), "krca_peer_score")
+        return out
+
+    def peer_score(self, v, groups, min_members=4, min_scale=0.0, out_thr=3.0):
+        """peer_score_device's dict (device tensors) plus host copies under '<key>_host' and the
+        arguments."""
+        v = self._dev(v, self.torch.float32)
+        d = self.peer_score_device(v, groups, min_members, min_scale, out_thr)
+        res = dict(d)
+        for key in self.PEER_KEYS:
+            res[key + "_host"] = d[key].cpu().numpy()
+        res["min_members"], res["min_scale"], res["out_thr"] = int(min_members), float(min_scale), float(out_thr)
         return res
 
     def rca_precede_device(self, onset, row_ptr, col, slack=0):

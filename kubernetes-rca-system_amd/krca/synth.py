@@ -243,6 +243,63 @@ def make_metrics_onsets(n_pods, n_metrics=8, n_steps=1440, window=60, seed=0, ro
     return x, onsets
 
 
+def make_metrics_replicas(n_pods, n_metrics=8, n_steps=200, seed=0, service_size=20, n_nodes=80, device="cpu",
+                          n_surges=0, n_faults=0, faults_in_surges=0, n_bad_nodes=0, t_fault=None, surge_sigma=16.0,
+                          fault_sigma=12.0, node_units=5.0, walk_sigma=0.2):
+    """Replica sets for the peer deviation score: pods in services of `service_size`
+    consecutive pods whose replicas share level, daily phase and amplitude, noise scale (within
+    +-15 %) and a load walk (a per-service random walk of walk_sigma noise deviations per step, the
+    same in every replica, loaded per metric by U(0.5, 1)); every node holds pods of many services
+    (a seeded permutation dealt round-robin over n_nodes).  From step t_fault (default T - 30) on:
+    n_surges whole services rise by surge_sigma deviations in every replica and metric, n_faults
+    single replicas of distinct services by fault_sigma (the first faults_in_surges of them inside
+    surging services, the others outside), and every pod of n_bad_nodes nodes gains node_units in
+    metric 0.  -> (x float32 [T, P, M] on `device`, info: "service" / "node" int32 [P] labels, "sigma"
+    float32 [P, M], "surges" (services), "faults" (pods), "bad_nodes" int64 arrays, sorted, "t_fault")."""
+    import torch
+    P, M, T, S = int(n_pods), int(n_metrics), int(n_steps), int(service_size)
+    g = torch.Generator(device=device)
+    g.manual_seed(int(seed))
+    rng = np.random.default_rng(int(seed) + 20202)
+    n_srv = max(1, math.ceil(P / S))
+    srv = torch.arange(P, device=device) // S
+    rand = lambda *shape: torch.rand(shape, generator=g, device=device)  # noqa: E731
+    b, a = rand(n_srv, M) * 30 + 25, rand(n_srv, M) * 12
+    sig_s, phi = rand(n_srv, M) * 2.5 + 0.5, rand(n_srv, 1) * (2 * math.pi)
+    load = rand(n_srv, M) * 0.5 + 0.5
+    sig = sig_s[srv] * (rand(P, M) * 0.3 + 0.85)
+    walk = torch.randn((T, n_srv), generator=g, device=device).cumsum_(0) * float(walk_sigma)
+    walk -= walk[T // 2:T // 2 + 1].clone()
+    tt = torch.arange(T, device=device, dtype=torch.float32).view(-1, 1, 1)
+    base = b + a * torch.sin(2 * math.pi * tt / 1440.0 + phi.view(1, n_srv, 1)) \
+        + walk.unsqueeze(2) * (load * sig_s).unsqueeze(0)                      # [T, n_srv, M]
+    x = base[:, srv, :] + sig * torch.randn((T, P, M), generator=g, device=device)
+    del base
+    node = np.empty(P, np.int32)
+    node[rng.permutation(P)] = np.arange(P, dtype=np.int32) % max(int(n_nodes), 1)
+    t0 = T - 30 if t_fault is None else int(t_fault)
+    full = np.flatnonzero(np.bincount(srv.cpu().numpy(), minlength=n_srv) == S)  # whole services only
+    pick = rng.permutation(full)
+    surges = np.sort(pick[:n_surges]).astype(np.int64)
+    inside = pick[:faults_in_surges]
+    outside = pick[n_surges:n_surges + n_faults - faults_in_surges]
+    faults = np.sort(np.concatenate([inside, outside]) * S + rng.integers(0, S, n_faults)).astype(np.int64)
+    bad_nodes = np.sort(rng.permutation(max(int(n_nodes), 1))[:n_bad_nodes]).astype(np.int64)
+    if len(surges):
+        sel = torch.as_tensor(np.flatnonzero(np.isin(np.arange(P) // S, surges)), device=device)
+        x[t0:, sel, :] += float(surge_sigma) * sig[sel]
+    if len(faults):
+        sel = torch.as_tensor(faults, device=device)
+        x[t0:, sel, :] += float(fault_sigma) * sig[sel]
+    if len(bad_nodes):
+        sel = torch.as_tensor(np.flatnonzero(np.isin(node, bad_nodes)), device=device)
+        x[t0:, sel, 0] += float(node_units)
+    x.clamp_(0.0, 100.0)
+    info = {"service": (np.arange(P) // S).astype(np.int32), "node": node, "sigma": sig.cpu().numpy(),
+            "surges": surges, "faults": faults, "bad_nodes": bad_nodes, "t_fault": t0}
+    return x, info
+
+
 def make_metrics_range(lo, hi, n_metrics=8, n_steps=1440, window=60, seed=0, roots=(), hop_sets=(), device="cpu",
                        block=62_500, **kw):
     """Pods [lo, hi) of a mesh-wide metric tensor, independent of how the pods are sharded: the
