@@ -279,11 +279,11 @@ int krca_log_scan(const uint8_t* text, int64_t nbytes, const int64_t* doc_off, i
  * ".*" between literals roughly doubles the states (one fits beside the 13 shipped patterns, two
  * pass KRCA_LOG_MAX_NSTATE).
  *
- * Long lines (over 1 KiB) take a wave per line, 64 segments.  log_dfa_long_rt starts each segment
+ * Long lines (over 1 KiB) take a wave per line, 64 segments.  log_dfa_long starts each segment
  * from the start state after a warm-up of `warm` code points (the longest alternative minus one):
  * exact only when no match is longer than warm + 1 code points, i.e. for fixed-length sets.  Tables
  * with KRCA_LOG_FLAG_CARRY (bit 0 of the header's flag word; the compiler sets it for a set with
- * loop items) take log_dfa_long_carry_rt instead: after the same speculative pass each lane compares
+ * loop items) take its carrying form instead: after the same speculative pass each lane compares
  * its entry state with its predecessor's exit state, and the lanes that differ re-walk their
  * segment from it, until a wave-wide vote finds no difference.  After round r lanes 0..r are final,
  * so at most 63 rounds and the result is exact for every DFA; `warm` (loops at their minimum, at

@@ -1,6 +1,6 @@
 // Device form of run-time log pattern tables (include/krca.h, "pattern tables compiled at run
-// time"): the LDS layout of log_dfa_rt / log_dfa_long_rt / log_dfa_long_carry_rt, shared by the host packer
-// (log_tables.cpp) and the kernels (log_rt.h).  All offsets in bytes, multiples of 16.
+// time"): the LDS layout of log_dfa / log_dfa_long over TabRt, shared by the host packer
+// (log_tables.cpp) and the table policy (log_rt.h).  All offsets in bytes, multiples of 16.
 #pragma once
 #include <stdint.h>
 

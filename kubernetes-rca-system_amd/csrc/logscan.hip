@@ -23,6 +23,9 @@
 // A/B paths (tests require identical outputs): KRCA_LOG_FUSED = 1 / 2, log_index_match walking the
 // DFA inside the index pass from the LDS-resident tile (+ the LOOK bytes after it, for its last line).
 // When the caller's line arrays are too small, krca_log_match finishes from the index in the workspace.
+// krca_log_scan_tables / krca_log_match_tables run the same kernels and launch sequences over a
+// pattern set compiled at run time: log_dfa and log_dfa_long take a table policy (log_rt.h: TabBuiltin,
+// TabRt), log_hist a category count, the launch sequences a Matcher.
 #include <stdint.h>
 #include <cstdlib>
 
@@ -782,9 +785,11 @@ constexpr int DFA_TPB = 512;
 //    identity column), no decode, when the block's line bytes are all ASCII; blocks holding a
 //    non-ASCII byte (or a code point continuing from the previous block) take the exact
 //    code-point path of the reference (decode, range table);
-//  * keeps a 32-bit entry per (state, symbol): the target's row offset (low half) and its
-//    category mask (high half), so the accept test is one OR per byte.
-// Per byte: a byte-table read, a 16-bit add, a table read and an OR.
+//  * (TabBuiltin) keeps a 32-bit entry per (state, symbol): the target's row offset (low half) and
+//    its category mask (high half), so the accept test is one OR per byte.
+// Per byte: a byte-table read, a 16-bit add, a table read and an OR.  What a table policy supplies
+// (log_rt.h) is the fill, the two symbol lookups, the 16 dependent steps of a block and the mask an
+// accumulator yields; TabRt pays an AND and a shift-add per step and reads out[] on flagged entries.
 constexpr int DFA_RS = 32;  // u32 entries per state row: the symbols, then NOP
 constexpr uint32_t NOP_SYM = DFA_RS - 1;
 // Row stride in the LDS table, in entries.  (A stride of 33 instead of 32 -- entry (state, symbol)
@@ -832,12 +837,13 @@ __device__ __forceinline__ uint32_t dfa4_step(const DfaLds4& d, uint32_t row, ui
 }
 
 // the DFA symbol of code point cp >= 0x80 (the reference's case folds and \d classes), by a binary
-// search of the range table copied to LDS (rng: KRCA_DFA_NRANGE x {lo, hi, symbol}; from constant
-// memory each probe was a dependent global load, ~7 per code point, and one line with a non-ASCII
-// character held its wave: +5k cycles per 64 KiB tile of log_index_match, r6n)
-__device__ __forceinline__ uint32_t cp_sym_lds(const uint32_t* rng, uint32_t cp) {
-  uint32_t sy = KRCA_DFA_OTHER;
-  int a = 0, z = KRCA_DFA_NRANGE - 1;
+// search of a range table in LDS (rng: nrange x {lo, hi, symbol}; the probes stay inside the nrange
+// triples whatever they hold.  From constant memory each probe was a dependent global load, ~7 per
+// code point, and one line with a non-ASCII character held its wave: +5k cycles per 64 KiB tile of
+// log_index_match, r6n)
+__device__ __forceinline__ uint32_t range_sym(const uint32_t* rng, int nrange, uint32_t other, uint32_t cp) {
+  uint32_t sy = other;
+  int a = 0, z = nrange - 1;
   while (a <= z) {
     const int mid = (a + z) >> 1;
     if (cp < rng[3 * mid]) z = mid - 1;
@@ -877,15 +883,16 @@ __device__ __forceinline__ uint32_t word_in_line(int j, uint32_t lo4, uint32_t h
   return ((idx | 0x80808080u) - lo4) & (hi4x - idx) & 0x80808080u;
 }
 
+#include "log_rt.h"  // TabBuiltin, TabRt<RSL>: the compiled-in patterns' tables and a run-time set's
+
+template <class Tab>
 __global__ __launch_bounds__(DFA_TPB) void log_dfa(const uint8_t* __restrict__ text, int64_t nbytes, int64_t L,
                                                    const int64_t* __restrict__ Ld, int64_t cap,
                                                    const int64_t* __restrict__ line_start,
                                                    const int64_t* __restrict__ line_end, uint32_t* __restrict__ line_mask,
-                                                   int32_t* __restrict__ long_q, int32_t* __restrict__ n_long) {
-  __shared__ DfaLds4 d;
-  __shared__ uint32_t d_rng[3 * KRCA_DFA_NRANGE];
-  load_ranges(d_rng);
-  dfa4_load(d);  // (its barrier covers d_rng)
+                                                   int32_t* __restrict__ long_q, int32_t* __restrict__ n_long,
+                                                   const Tab T) {
+  T.fill_walk();
   L = lines_of(L, Ld, cap);
   for (int64_t l0 = (int64_t)blockIdx.x * DFA_TPB; l0 < L; l0 += (int64_t)gridDim.x * DFA_TPB) {
     // buffer resource at the group's first line: offsets stay 32-bit (the group's short lines
@@ -901,7 +908,7 @@ __global__ __launch_bounds__(DFA_TPB) void log_dfa(const uint8_t* __restrict__ t
       long_q[atomicAdd(n_long, 1)] = (int32_t)l;  // a wave per long line (log_dfa_long)
       continue;
     }
-    uint32_t row = 0, acc = 0;
+    uint32_t st = 0, acc = 0;                    // st: the last table entry read
     int off = (int)((s & ~(int64_t)3) - base);  // this block's first byte, from base
     int rs_ = (int)(s & 3);                      // s - P: 0..3 at the first block, then negative
     int re_ = (int)(e - (s & ~(int64_t)3));      // e - P
@@ -935,7 +942,7 @@ __global__ __launch_bounds__(DFA_TPB) void log_dfa(const uint8_t* __restrict__ t
         hib |= w[j] & in;
         const uint32_t x = w[j] | (in ^ 0x80808080u);  // outside the line: >= 0x80, NOP
 #pragma unroll
-        for (int k = 0; k < 4; ++k) so[4 * j + k] = d.sym[(x >> (8 * k)) & 0xFFu];
+        for (int k = 0; k < 4; ++k) so[4 * j + k] = T.byte_off((x >> (8 * k)) & 0xFFu);
       }
       if (hib) {  // in-line bytes >= 0x80 (rare): the lead bytes' code points
 #pragma unroll
@@ -947,16 +954,11 @@ __global__ __launch_bounds__(DFA_TPB) void log_dfa(const uint8_t* __restrict__ t
               if (q < 16) return (w[q >> 2] >> (8 * (q & 3))) & 0xFFu;
               return off + q < end_off ? (uint32_t)text[base + off + q] : 0u;
             });
-            so[k] = cp_sym_lds(d_rng, cp) * 4;
+            so[k] = T.cp_off(cp);
           }
         }
       }
-#pragma unroll
-      for (int k = 0; k < 16; ++k) {
-        const uint32_t t = dfa4_step(d, row, so[k]);
-        row = t;
-        acc |= t;
-      }
+      T.steps(so, st, acc);  // the 16 dependent steps
       const bool more = re_ > 16;
       off += 16;
       rs_ -= 16;
@@ -968,33 +970,50 @@ __global__ __launch_bounds__(DFA_TPB) void log_dfa(const uint8_t* __restrict__ t
       while (block(R0, R2) && block(R1, R0) && block(R2, R1)) {
       }
     }
-    line_mask[l] = acc >> 16;
+    line_mask[l] = T.line_mask(acc);
   }
 }
 
+// ---- log_dfa_long: a wave per line over 1 KiB, 64 segments, each warmed up over the T.warm() code
+// points before it (the set's longest alternative minus one; 23 for the compiled-in patterns), the
+// segments' masks OR-reduced across the wave.
+// CARRY: for tables with KRCA_LOG_FLAG_CARRY (loop items: a match has no longest length, so no
+// warm-up makes a segment's start state right; without it the round loop below is the first walk alone).
+// Same segments, same warm-up and first walk; then the state is carried along the wave.  Per round:
+// prev = the predecessor lane's exit state (the start state for lane 0); a wave-wide vote -- executed by
+// all 64 lanes, those with an empty segment included -- ends the line when no lane has prev != entry;
+// else the lanes that differ take prev as their entry and walk their segment again.  After round r
+// lanes 0..r hold the true states, so the loop ends within 63 rounds for every table (the bound is
+// also its trip count).  Masks of superseded walks stay ORed in: every walk starts from the state that
+// some suffix of the text before its segment leads to from the start state, so what it reports is a
+// match inside the line, and the last walk of every lane is the true one.  An empty segment hands its
+// entry on.  Worst case: a state that survives every boundary (".*" armed in segment 0) makes lane r
+// walk in round r alone -- one serial walk of the line.  No workspace, no atomics; reads the bytes the
+// first walk reads.
+template <class Tab, bool CARRY>
 __global__ __launch_bounds__(TPB) void log_dfa_long(const uint8_t* __restrict__ text, int64_t nbytes,
                                                     const int64_t* __restrict__ line_start,
                                                     const int64_t* __restrict__ line_end,
                                                     uint32_t* __restrict__ line_mask, const int32_t* __restrict__ long_q,
-                                                    const int32_t* __restrict__ n_long) {
-  __shared__ DfaLds dfa;
+                                                    const int32_t* __restrict__ n_long, const Tab T) {
   const int nq = *n_long;
   if ((int64_t)blockIdx.x * (TPB / 64) >= nq) return;  // no long line for this block: skip the table fill
-  dfa_load(dfa);
+  T.fill_long();
   const int lane = threadIdx.x & 63;
   Bytes B;
   B.init(text, nbytes);
+  // (j is the same for the 64 lanes of a wave: the shuffles and the vote below run with every lane active)
   for (int j = (int)(blockIdx.x * (TPB / 64) + (threadIdx.x >> 6)); j < nq; j += (int)(gridDim.x * (TPB / 64))) {
     const int64_t l = long_q[j];
     const int64_t s = line_start[l], e = line_end[l];
     const int64_t seg = (e - s + 63) / 64;
     const int64_t a = min(e, s + lane * seg), b = min(e, a + seg);
-    uint32_t row = 0, mask = 0;
+    uint32_t st_in = 0, mask = 0;
     const int64_t p0 = a > s ? cp_align(B, a, e) : s;  // first code point starting in [a, b)
-    if (p0 > s && p0 < b) {  // warm-up over the <= WARM code points of the line before p0
+    if (p0 > s && p0 < b) {  // warm-up over the <= warm code points of the line before p0 (CARRY: speculation only)
       int64_t k = p0;
       int seen = 0;
-      while (k > s && seen < WARM) {
+      while (k > s && seen < T.warm()) {
         const uint32_t c = B.at(k - 1);
         --k;
         if ((c & 0xC0) != 0x80) ++seen;
@@ -1002,17 +1021,31 @@ __global__ __launch_bounds__(TPB) void log_dfa_long(const uint8_t* __restrict__ 
       while (k < p0) {
         uint32_t cp;
         const int len = decode(B, k, cp);
-        row = dfa.trans[row + cp_symbol(dfa, cp)] & (kAcc - 1);
+        st_in = T.state(T.step(st_in, cp));
         k += len;
       }
     }
-    for (int64_t p = p0; p < b;) {
-      uint32_t cp;
-      const int len = decode(B, p, cp);
-      const uint32_t t = dfa.trans[row + cp_symbol(dfa, cp)];
-      row = t & (kAcc - 1);
-      if (__builtin_expect((t & kAcc) != 0, 0)) mask |= dfa.out[row / KRCA_DFA_NSYM];
-      p += len;
+    uint32_t st_out = 0;
+    bool redo = true;  // round 0: every lane's first walk
+    for (int round = 0;; ++round) {
+      if (redo) {  // [p0, b) from st_in (an empty segment hands it on)
+        uint32_t st = st_in;
+        for (int64_t p = p0; p < b;) {
+          uint32_t cp;
+          const int len = decode(B, p, cp);
+          const uint32_t t = T.step(st, cp);
+          st = T.state(t);
+          if (__builtin_expect(T.accepts(t), 0)) mask |= T.mask(st);
+          p += len;
+        }
+        st_out = st;
+      }
+      if (!CARRY || round == 63) break;
+      uint32_t prev = __shfl_up(st_out, 1, 64);
+      if (lane == 0) prev = 0;
+      redo = prev != st_in;
+      if (!__any(redo)) break;
+      if (redo) st_in = prev;
     }
     for (int off = 32; off > 0; off >>= 1) mask |= __shfl_xor(mask, off, 64);
     if (lane == 0) line_mask[l] = mask;
@@ -1046,25 +1079,42 @@ __device__ __forceinline__ int64_t first_line_at(const int64_t* __restrict__ lin
 // lines of its container in category c (the reference's evidence, ref:agents/logs_agent.py:159-163),
 // so the examples cost no more than the masks they sit beside (a dense [D][13][3] id table is 156 B
 // per container: 2/3 of the scan's writes at C5).  DENSE also writes that table (A/B, compat).
-constexpr uint32_t CAT_BITS = (1u << KRCA_NCAT) - 1u;
 constexpr int EX_SHIFT = 16;
-static_assert(EX_SHIFT + KRCA_NCAT <= 32, "example bits must fit the line mask");
+static_assert(EX_SHIFT + KRCA_LOG_MAX_NCAT <= 32, "example bits must fit the line mask");
 
-template <bool DENSE>
+// The category count of log_hist: CAP sizes the per-lane arrays, the LDS rows and the unrolled loops;
+// n() is the width of the output rows; at(i, w) is where element i of a block's output of w values per
+// category sits in LDS rows of CAP * w.
+struct CatsFixed {  // the compiled-in patterns: every bound and index a constant
+  static constexpr int CAP = KRCA_NCAT;
+  __device__ __forceinline__ constexpr int n() const { return KRCA_NCAT; }
+  __device__ __forceinline__ int at(int i, int) const { return i; }
+};
+struct CatsRt {  // a run-time set (a kernel argument): ncat <= KRCA_LOG_MAX_NCAT
+  static constexpr int CAP = KRCA_LOG_MAX_NCAT;
+  int ncat;
+  __device__ __forceinline__ int n() const { return ncat; }
+  __device__ __forceinline__ int at(int i, int w) const { return (i / (ncat * w)) * CAP * w + i % (ncat * w); }
+};
+
+template <bool DENSE, class Cats>
 __global__ __launch_bounds__(TPB) void log_hist(const int64_t* __restrict__ doc_off, int64_t D,
                                                 const int64_t* __restrict__ chunk_line0, int64_t nchunks,
                                                 const int64_t* __restrict__ line_start,
                                                 uint32_t* __restrict__ line_mask, int64_t L,
                                                 const int64_t* __restrict__ Ld, int64_t cap,
                                                 int32_t* __restrict__ doc_lines, int32_t* __restrict__ hist,
-                                                int32_t* __restrict__ examples, int64_t* __restrict__ doc_line0) {
+                                                int32_t* __restrict__ examples, int64_t* __restrict__ doc_line0,
+                                                const Cats cats) {
+  constexpr int NC = Cats::CAP;
   // the block's histograms (and dense examples) are assembled in LDS and leave in coalesced rows (a
   // lane writing its own 52 ints at a 208-byte stride touched ~26 lines per store instruction)
-  __shared__ int32_t s_ex[TPB * KRCA_NCAT * (DENSE ? 3 : 1)];
+  __shared__ int32_t s_ex[TPB * NC * (DENSE ? 3 : 1)];
+  const uint32_t cat_bits = (1u << cats.n()) - 1u;
   L = lines_of(L, Ld, cap);
-  int32_t mycnt[KRCA_NCAT];  // this lane's container histogram (small or big path)
+  int32_t mycnt[NC];  // this lane's container histogram (small or big path)
 #pragma unroll
-  for (int c = 0; c < KRCA_NCAT; ++c) mycnt[c] = 0;
+  for (int c = 0; c < NC; ++c) mycnt[c] = 0;
   const int64_t d0 = (int64_t)blockIdx.x * TPB;
   const int64_t d = d0 + threadIdx.x;
   const int lane = threadIdx.x & 63;
@@ -1074,19 +1124,19 @@ __global__ __launch_bounds__(TPB) void log_hist(const int64_t* __restrict__ doc_
   if (valid && (lane == 63 || d + 1 == D)) hi = first_line_at(line_start, L, chunk_line0, nchunks, doc_off[d + 1]);
   const bool small = valid && hi - lo <= HIST_SMALL;
   if (small) {
-    int32_t cnt[KRCA_NCAT], ex[KRCA_NCAT][3];
+    int32_t cnt[NC], ex[NC][3];
 #pragma unroll
-    for (int c = 0; c < KRCA_NCAT; ++c) {
+    for (int c = 0; c < NC; ++c) {
       cnt[c] = 0;
       ex[c][0] = ex[c][1] = ex[c][2] = -1;
     }
     uint32_t full = 0;  // bins holding three examples already
     for (int64_t l = lo; l < hi; ++l) {
-      const uint32_t m = line_mask[l] & CAT_BITS;
+      const uint32_t m = line_mask[l] & cat_bits;
       const uint32_t exb = m & ~full;
       if (exb) line_mask[l] = m | (exb << EX_SHIFT);
 #pragma unroll
-      for (int c = 0; c < KRCA_NCAT; ++c) {
+      for (int c = 0; c < NC; ++c) {
         if ((m >> c) & 1u) {
           const int f = cnt[c];
           if (DENSE) {
@@ -1102,11 +1152,11 @@ __global__ __launch_bounds__(TPB) void log_hist(const int64_t* __restrict__ doc_
     doc_lines[d] = (int32_t)(hi - lo);
     if (doc_line0) doc_line0[d] = lo;
 #pragma unroll
-    for (int c = 0; c < KRCA_NCAT; ++c) mycnt[c] = cnt[c];
+    for (int c = 0; c < NC; ++c) mycnt[c] = cnt[c];
     if (DENSE) {
-      int32_t* ed = s_ex + threadIdx.x * KRCA_NCAT * 3;
+      int32_t* ed = s_ex + threadIdx.x * NC * 3;
 #pragma unroll
-      for (int c = 0; c < KRCA_NCAT; ++c) {
+      for (int c = 0; c < NC; ++c) {
         ed[c * 3] = ex[c][0];
         ed[c * 3 + 1] = ex[c][1];
         ed[c * 3 + 2] = ex[c][2];
@@ -1120,16 +1170,16 @@ __global__ __launch_bounds__(TPB) void log_hist(const int64_t* __restrict__ doc_
     big &= big - 1;
     const int64_t dj = d - lane + j;
     const int64_t blo = __shfl(lo, j, 64), bhi = __shfl(hi, j, 64);
-    int32_t cnt[KRCA_NCAT];
+    int32_t cnt[NC];
 #pragma unroll
-    for (int c = 0; c < KRCA_NCAT; ++c) cnt[c] = 0;
-    int32_t* ex = s_ex + (threadIdx.x - lane + j) * KRCA_NCAT * 3;
+    for (int c = 0; c < NC; ++c) cnt[c] = 0;
+    int32_t* ex = s_ex + (threadIdx.x - lane + j) * NC * 3;
     for (int64_t b = blo; b < bhi; b += 64) {
       const bool in = b + lane < bhi;
-      const uint32_t m = in ? (line_mask[b + lane] & CAT_BITS) : 0u;
+      const uint32_t m = in ? (line_mask[b + lane] & cat_bits) : 0u;
       uint32_t exb = 0;
 #pragma unroll
-      for (int c = 0; c < KRCA_NCAT; ++c) {
+      for (int c = 0; c < NC; ++c) {
         const uint64_t bal = __ballot((m >> c) & 1u);
         const int f = cnt[c];  // wave-uniform
         // this line is an example of bin c when fewer than three came before it in the container
@@ -1148,14 +1198,14 @@ __global__ __launch_bounds__(TPB) void log_hist(const int64_t* __restrict__ doc_
     }
     if (lane == j) {  // counts are wave-uniform (ballots): the container's own lane keeps them
 #pragma unroll
-      for (int c = 0; c < KRCA_NCAT; ++c) mycnt[c] = cnt[c];
+      for (int c = 0; c < NC; ++c) mycnt[c] = cnt[c];
     }
     if (lane == 0) {
       doc_lines[dj] = (int32_t)(bhi - blo);
       if (doc_line0) doc_line0[dj] = blo;
       if (DENSE) {
 #pragma unroll
-        for (int c = 0; c < KRCA_NCAT; ++c)
+        for (int c = 0; c < NC; ++c)
           for (int k = cnt[c] < 3 ? cnt[c] : 3; k < 3; ++k) ex[c * 3 + k] = -1;
       }
     }
@@ -1163,13 +1213,14 @@ __global__ __launch_bounds__(TPB) void log_hist(const int64_t* __restrict__ doc_
   const int nv = (int)(D - d0 < TPB ? D - d0 : TPB);
   if (DENSE) {
     __syncthreads();
-    for (int i = threadIdx.x; i < nv * KRCA_NCAT * 3; i += TPB) examples[d0 * KRCA_NCAT * 3 + i] = s_ex[i];
+    const int row = cats.n() * 3;
+    for (int i = threadIdx.x; i < nv * row; i += TPB) examples[d0 * row + i] = s_ex[cats.at(i, 3)];
   }
   __syncthreads();  // the buffer now takes the histograms
 #pragma unroll
-  for (int c = 0; c < KRCA_NCAT; ++c) s_ex[threadIdx.x * KRCA_NCAT + c] = mycnt[c];
+  for (int c = 0; c < NC; ++c) s_ex[threadIdx.x * NC + c] = mycnt[c];
   __syncthreads();
-  for (int i = threadIdx.x; i < nv * KRCA_NCAT; i += TPB) hist[d0 * KRCA_NCAT + i] = s_ex[i];
+  for (int i = threadIdx.x; i < nv * cats.n(); i += TPB) hist[d0 * cats.n() + i] = s_ex[cats.at(i, 1)];
 }
 
 // ---- log_index_match: line index AND DFA walk in ONE pass over the text (round 4) ------------
@@ -1310,7 +1361,7 @@ __device__ __forceinline__ uint32_t sym_word(const uint8_t* conv, uint32_t w) {
 // the symbol offset of code point cp >= 0x80 in TAB's rows
 template <class TAB>
 __device__ __forceinline__ uint32_t cp_symoff(const TAB& d, const uint32_t* rng, uint32_t cp) {
-  return cp_sym_lds(rng, cp) * dsym_scale(d);
+  return range_sym(rng, KRCA_DFA_NRANGE, KRCA_DFA_OTHER, cp) * dsym_scale(d);
 }
 
 // The DFA mask of the line at tile offsets [s, e) from s_text (e <= FTILE + LOOK; the array is
@@ -1717,7 +1768,265 @@ LogWs log_ws(int64_t* ws, int64_t nbytes) {
   return w;
 }
 
-#include "log_rt.h"  // the kernels over pattern tables compiled at run time
+// ---- launches: what differs between the compiled-in patterns and a run-time set is a Matcher ----------
+struct LogArgs {  // the arguments the four scan / match entry points share
+  const uint8_t* text;
+  int64_t nbytes;
+  const int64_t* doc_off;
+  int64_t ndocs;
+  int64_t* ws;
+  int64_t *line_start, *line_end;
+  uint32_t* line_mask;
+  int32_t *doc_lines, *hist, *examples;
+  int64_t* doc_line0;
+  void* stream;
+};
+struct Lines {  // how many lines the line arrays hold: L, or with Ld (the count on the device) min(*Ld, cap)
+  int64_t L;
+  const int64_t* Ld;
+  int64_t cap;
+  int64_t bound() const { return Ld ? cap : L; }
+};
+
+struct Matcher {
+  int ncat = KRCA_NCAT;
+  virtual int fused() const { return 0; }  // KRCA_LOG_FUSED: the walk inside the index pass
+  // decides the launches; may refuse (KRCA_EINVAL) before the first of them
+  virtual int prepare(const char* who, hipStream_t st) { return KRCA_OK; }
+  // the lockstep walk (unless the fused index pass has walked the short lines), then the long lines
+  virtual void walk(hipStream_t st, const LogArgs& a, const LogWs& w, const Lines& ln, bool lockstep) const = 0;
+  virtual void hist(hipStream_t st, const LogArgs& a, const LogWs& w, const Lines& ln) const = 0;
+};
+
+template <class Cats>
+void launch_hist(hipStream_t st, const LogArgs& a, const LogWs& w, const Lines& ln, Cats cats) {
+  hipLaunchKernelGGL((a.examples ? log_hist<true, Cats> : log_hist<false, Cats>), dim3((unsigned)krca::ceil_div(a.ndocs, TPB)),
+                     dim3(TPB), 0, st, a.doc_off, a.ndocs, (const int64_t*)w.chunk_line0, w.nt * TPB,
+                     (const int64_t*)a.line_start, a.line_mask, ln.L, ln.Ld, ln.cap, a.doc_lines, a.hist, a.examples,
+                     a.doc_line0, cats);
+}
+
+struct BuiltinMatcher : Matcher {
+  int fused() const override { return krca::tuning().log_fused; }
+  void walk(hipStream_t st, const LogArgs& a, const LogWs& w, const Lines& ln, bool lockstep) const override {
+    if (lockstep) {  // persistent: the 50 KB table is filled once per workgroup, 3 workgroups per CU
+      const int64_t grid = std::max<int64_t>(1, std::min<int64_t>(krca::ceil_div(ln.bound(), DFA_TPB), 256 * 3));
+      hipLaunchKernelGGL(log_dfa<TabBuiltin>, dim3((unsigned)grid), dim3(DFA_TPB), 0, st, a.text, a.nbytes, ln.L, ln.Ld, ln.cap,
+                         (const int64_t*)a.line_start, (const int64_t*)a.line_end, a.line_mask, w.long_q, w.n_long,
+                         TabBuiltin{});
+    }
+    hipLaunchKernelGGL((log_dfa_long<TabBuiltin, false>), dim3(256), dim3(TPB), 0, st, a.text, a.nbytes,
+                       (const int64_t*)a.line_start, (const int64_t*)a.line_end, a.line_mask, (const int32_t*)w.long_q,
+                       (const int32_t*)w.n_long, TabBuiltin{});
+  }
+  void hist(hipStream_t st, const LogArgs& a, const LogWs& w, const Lines& ln) const override {
+    launch_hist(st, a, w, ln, CatsFixed{});
+  }
+};
+
+// workgroups per CU x CUs for `kernel` with `lds` bytes of dynamic LDS, after opting in above the default
+// per-workgroup limit; KRCA_EINVAL (before any launch) when the runtime cannot launch it
+int rt_prepare(const void* kernel, const char* name, int tpb, uint32_t lds, hipStream_t st, int64_t* resident,
+               std::atomic<uint32_t>& asked) {
+  int dev = 0;
+  KRCA_HIP(st ? hipStreamGetDevice(st, &dev) : hipGetDevice(&dev));
+  int base = 0, cus = 0;
+  KRCA_HIP(hipDeviceGetAttribute(&base, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
+  KRCA_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+  hipFuncAttributes fa;
+  KRCA_HIP(hipFuncGetAttributes(&fa, kernel));
+  if ((int64_t)fa.sharedSizeBytes + lds > (int64_t)base) {  // above the default: opt in (the runtime refuses what the CU lacks)
+    // never below what an earlier call opted in to (another thread may be launching with it)
+    uint32_t want = asked.load();
+    while (want < lds && !asked.compare_exchange_weak(want, lds)) {
+    }
+    const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)std::max(want, lds));
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      krca::set_error("%s: a pattern table of %u bytes of LDS cannot launch on this device (default limit %d bytes, opt-in "
+                      "refused: %s)", name, lds, base, hipGetErrorString(e));
+      return KRCA_EINVAL;
+    }
+  }
+  int per_cu = 0;
+  const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, tpb, lds);
+  if (e != hipSuccess || per_cu < 1) {
+    (void)hipGetLastError();
+    krca::set_error("%s: no workgroup with a pattern table of %u bytes of LDS fits a compute unit of this device", name, lds);
+    return KRCA_EINVAL;
+  }
+  *resident = (int64_t)per_cu * std::max(cus, 1);
+  return KRCA_OK;
+}
+
+struct RtMatcher : Matcher {  // a set compiled at run time: the caller's device tables and their dimensions
+  const void* tables_dev;
+  int64_t tables_dev_bytes;
+  const krca_log_dims* dims;
+  RtMatcher(const void* t, int64_t bytes, const krca_log_dims* d) : tables_dev(t), tables_dev_bytes(bytes), dims(d) {}
+  // decided by prepare(), before the first kernel
+  RtDims dm;
+  int rsl;
+  bool carry;  // KRCA_LOG_FLAG_CARRY: the long lines' walk carries the state along the wave
+  int64_t walk_resident, long_resident;
+
+  template <int RSL>
+  int plan(hipStream_t st) {
+    // the runtime's answers for the last (device, table size) of this thread: a scan per window asks once, not
+    // five host queries in front of every scan's first launch
+    static thread_local struct { int dev; uint32_t bytes; bool carry; int64_t walk, lng; } last = {-1, 0, false, 0, 0};
+    int dev = 0;
+    KRCA_HIP(st ? hipStreamGetDevice(st, &dev) : hipGetDevice(&dev));
+    if (last.dev == dev && last.bytes == dm.bytes && last.carry == carry) {
+      walk_resident = last.walk, long_resident = last.lng;
+      return KRCA_OK;
+    }
+    static std::atomic<uint32_t> asked_walk{0}, asked_long{0}, asked_carry{0};  // largest opt-in requested per kernel
+    using T = TabRt<RSL>;
+    int rc = rt_prepare(reinterpret_cast<const void*>(&log_dfa<T>), "log_dfa", DFA_TPB, dm.bytes, st, &walk_resident, asked_walk);
+    if (!rc)
+      rc = rt_prepare(reinterpret_cast<const void*>(carry ? &log_dfa_long<T, true> : &log_dfa_long<T, false>), "log_dfa_long",
+                      TPB, dm.bytes, st, &long_resident, carry ? asked_carry : asked_long);
+    if (!rc) last = {dev, dm.bytes, carry, walk_resident, long_resident};
+    return rc;
+  }
+  int prepare(const char* who, hipStream_t st) override {
+    KRCA_CHECK_ARG(tables_dev && dims, "%s: null pattern tables", who);
+    KRCA_CHECK_ARG(krca::log_dims_ok(*dims), "%s: table dimensions outside the limits of include/krca.h", who);
+    const krca::LogRtLayout l = krca::log_rt_layout(*dims);
+    KRCA_CHECK_ARG(tables_dev_bytes >= (int64_t)l.bytes, "%s: device tables of %lld bytes, these dimensions need %u", who,
+                   (long long)tables_dev_bytes, l.bytes);
+    KRCA_CHECK_ARG(((uintptr_t)tables_dev & 3) == 0, "%s: device tables must be 4-byte aligned", who);
+    const krca_log_dims& d = *dims;
+    dm.ncat = d.ncat, dm.nsym = d.nsym, dm.nstate = d.nstate, dm.nrange = d.nrange, dm.warm = d.warm, dm.other = d.other;
+    dm.out_off = l.out_off, dm.sym_off = l.sym_off, dm.rng_off = l.rng_off, dm.bytes = l.bytes;
+    ncat = d.ncat;
+    rsl = l.rsl;
+    carry = (d.flags & KRCA_LOG_FLAG_CARRY) != 0;
+    return rsl == 5 ? plan<5>(st) : plan<6>(st);
+  }
+
+  template <int RSL>
+  void walk_t(hipStream_t st, const LogArgs& a, const LogWs& w, const Lines& ln) const {
+    using T = TabRt<RSL>;
+    const T tab{static_cast<const uint8_t*>(tables_dev), dm};
+    const int64_t grid = std::max<int64_t>(1, std::min<int64_t>(krca::ceil_div(ln.bound(), DFA_TPB), walk_resident));
+    hipLaunchKernelGGL(log_dfa<T>, dim3((unsigned)grid), dim3(DFA_TPB), dm.bytes, st, a.text, a.nbytes, ln.L, ln.Ld, ln.cap,
+                       (const int64_t*)a.line_start, (const int64_t*)a.line_end, a.line_mask, w.long_q, w.n_long, tab);
+    const int64_t grid_long = std::max<int64_t>(1, std::min<int64_t>(256, long_resident));
+    hipLaunchKernelGGL((carry ? log_dfa_long<T, true> : log_dfa_long<T, false>), dim3((unsigned)grid_long), dim3(TPB), dm.bytes,
+                       st, a.text, a.nbytes, (const int64_t*)a.line_start, (const int64_t*)a.line_end, a.line_mask,
+                       (const int32_t*)w.long_q, (const int32_t*)w.n_long, tab);
+  }
+  void walk(hipStream_t st, const LogArgs& a, const LogWs& w, const Lines& ln, bool) const override {
+    if (rsl == 5) walk_t<5>(st, a, w, ln);
+    else walk_t<6>(st, a, w, ln);
+  }
+  void hist(hipStream_t st, const LogArgs& a, const LogWs& w, const Lines& ln) const override {
+    launch_hist(st, a, w, ln, CatsRt{ncat});
+  }
+};
+
+// krca_log_match / krca_log_match_tables: the line arrays from the index in the workspace (n_lines known), the
+// walk, the histograms
+int log_match_seq(const char* who, Matcher&& m, const LogArgs& a, int64_t n_lines) {
+  KRCA_CHECK_ARG(a.nbytes >= 0 && a.ndocs >= 1 && n_lines >= 0, "%s: bad sizes", who);
+  KRCA_CHECK_ARG(a.doc_off && a.ws && a.doc_lines && a.hist, "%s: null pointer", who);
+  KRCA_CHECK_ARG(((uintptr_t)a.text & 15) == 0, "%s: text must be 16-byte aligned", who);
+  KRCA_CHECK_ARG(n_lines == 0 || (a.line_start && a.line_end && a.line_mask), "%s: null line arrays", who);
+  hipStream_t st = krca::as_stream(a.stream);
+  const int rc = m.prepare(who, st);
+  if (rc) return rc;
+  const LogWs w = log_ws(a.ws, a.nbytes);
+  const Lines ln{n_lines, nullptr, 0};
+  if (n_lines > 0) {  // line offsets from the index, then a DFA lane per line (long lines: a wave each)
+    KRCA_HIP(hipMemsetAsync(w.n_long, 0, sizeof(int32_t), st));
+    hipLaunchKernelGGL(log_lines, dim3((unsigned)w.nt), dim3(TPB), 0, st, a.text, a.nbytes, a.doc_off, a.ndocs,
+                       (const int32_t*)w.cdoc, (const int32_t*)w.chunk, (const int64_t*)w.tile, n_lines, a.line_start,
+                       a.line_end, w.chunk_line0);
+    KRCA_LAUNCH_CHECK();
+    hipLaunchKernelGGL(log_last_end, dim3(1), dim3(1), 0, st, a.text, a.nbytes, a.doc_off, a.ndocs, n_lines,
+                       (const int64_t*)nullptr, (int64_t)0, a.line_end);
+    KRCA_LAUNCH_CHECK();
+    m.walk(st, a, w, ln, true);
+    KRCA_LAUNCH_CHECK();
+  } else {  // no lines: chunk_line0 = 0 for log_hist
+    KRCA_HIP(hipMemsetAsync(w.chunk_line0, 0, w.nt * TPB * sizeof(int64_t), st));
+  }
+  m.hist(st, a, w, ln);
+  KRCA_LAUNCH_CHECK();
+  return KRCA_OK;
+}
+
+// krca_log_scan / krca_log_scan_tables: index, walk and histograms in one call; the line count stays on the
+// device until the read-back that ends the call
+int log_scan_seq(const char* who, Matcher&& m, const LogArgs& a, int64_t line_cap, int64_t* n_lines_host) {
+  KRCA_CHECK_ARG(a.nbytes >= 0 && a.ndocs >= 1 && a.ndocs < INT32_MAX && line_cap >= 0, "%s: bad sizes", who);
+  KRCA_CHECK_ARG(a.doc_off && a.ws && a.doc_lines && a.hist && n_lines_host, "%s: null pointer", who);
+  KRCA_CHECK_ARG(a.nbytes == 0 || a.text, "%s: null text", who);
+  KRCA_CHECK_ARG(((uintptr_t)a.text & 15) == 0, "%s: text must be 16-byte aligned", who);
+  KRCA_CHECK_ARG(line_cap == 0 || (a.line_start && a.line_end && a.line_mask), "%s: null line arrays", who);
+  hipStream_t st = krca::as_stream(a.stream);
+  const int rc = m.prepare(who, st);
+  if (rc) return rc;
+  const LogWs w = log_ws(a.ws, a.nbytes);
+  const int64_t nt = w.nt, ndocs = a.ndocs, nbytes = a.nbytes;
+  int64_t* const tile = w.tile;  // tile[nt] = the line count, on the device
+  if (nbytes == 0) {
+    // no text (the pointer may be null): every container is empty and no kernel may read text --
+    // the index pass's unconditional piece loads clamp to the last 16-byte block that holds a
+    // byte, and there is none (an empty window faulted there: test_log_scan_degenerate_texts)
+    KRCA_HIP(hipMemsetAsync(tile, 0, (nt + 1) * sizeof(int64_t), st));  // tile bases, the line count
+    KRCA_HIP(hipMemsetAsync(w.chunk_line0, 0, nt * TPB * sizeof(int64_t), st));
+    KRCA_HIP(hipMemsetAsync(a.doc_lines, 0, ndocs * sizeof(int32_t), st));
+    KRCA_HIP(hipMemsetAsync(a.hist, 0, ndocs * m.ncat * sizeof(int32_t), st));
+    if (a.examples) KRCA_HIP(hipMemsetAsync(a.examples, 0xFF, ndocs * m.ncat * 3 * sizeof(int32_t), st));  // -1
+    if (a.doc_line0) KRCA_HIP(hipMemsetAsync(a.doc_line0, 0, ndocs * sizeof(int64_t), st));
+    *n_lines_host = 0;
+    return KRCA_OK;
+  }
+  // one launch before the index: the chunk -> container map (every chunk of the text is written
+  // under the doc_off contract; off it, tile_container_starts clamps what it reads), and the zeroed
+  // look-back status words + ticket and long-line count (no memset launches: each dependent
+  // launch costs ~10 us at the front of the scan)
+  hipLaunchKernelGGL(log_chunk_doc, dim3((unsigned)krca::ceil_div(ndocs, TPB)), dim3(TPB), 0, st, a.doc_off, ndocs,
+                     nbytes, w.cdoc, w.status, 2 * nt + 1, w.n_long);  // status words, ticket
+  KRCA_LAUNCH_CHECK();
+  const Lines ln{0, tile + nt, line_cap};  // the line count, on the device (written by the index's last tile)
+  const int fused = m.fused();
+  if (fused) {
+    // A/B: the line index and the DFA walk in one pass over the text (KRCA_LOG_FUSED = 1: 32 KiB
+    // tiles, two 512-thread workgroups per CU; 2: 64 KiB tiles, one 1024-thread workgroup per CU);
+    // long lines go to log_dfa_long.  It reads the text once but runs its phases one after the
+    // other per tile (DESIGN §3.3)
+    auto launch = [&](auto cfg) {
+      using CF = decltype(cfg);
+      const int64_t ntf = num_ftiles(nbytes, CF::FTILE);
+      const int64_t resident =
+          krca::resident_workgroups(reinterpret_cast<const void*>(&log_index_match<CF>), CF::FTPB, st, 1);
+      hipLaunchKernelGGL(log_index_match<CF>, dim3((unsigned)std::min<int64_t>(ntf, resident)), dim3(CF::FTPB), 0, st,
+                         a.text, nbytes, a.doc_off, ndocs, (const int32_t*)w.cdoc, w.chunk, tile, nt, w.status, w.ticket,
+                         ntf, line_cap, a.line_start, a.line_end, a.line_mask, w.chunk_line0, tile + nt, w.long_q, w.n_long);
+    };
+    if (fused == 2) launch(FBig{});
+    else launch(FSmall{});
+  } else {  // default (KRCA_LOG_FUSED=0): the line index, then a DFA lane per line re-reading the text
+    // workgroups the stream's device keeps resident (occupancy API, cached per device)
+    const int64_t resident = krca::resident_workgroups(reinterpret_cast<const void*>(&log_index_lines), TPB, st, 4);
+    const int64_t grid_ix = LOG_IDX_PERSIST ? std::min<int64_t>(nt, resident) : nt;
+    hipLaunchKernelGGL(log_index_lines, dim3((unsigned)grid_ix), dim3(TPB), 0, st, a.text, nbytes, a.doc_off, ndocs,
+                       (const int32_t*)w.cdoc, w.chunk, tile, w.status, w.ticket, nt, line_cap, a.line_start, a.line_end,
+                       w.chunk_line0, tile + nt);
+  }
+  KRCA_LAUNCH_CHECK();
+  m.walk(st, a, w, ln, !fused);
+  KRCA_LAUNCH_CHECK();
+  m.hist(st, a, w, ln);
+  KRCA_LAUNCH_CHECK();
+  KRCA_HIP(hipMemcpyAsync(n_lines_host, ln.Ld, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  KRCA_HIP(hipStreamSynchronize(st));
+  return KRCA_OK;
+}
 
 }  // namespace
 
@@ -1753,118 +2062,19 @@ int krca_log_index(const uint8_t* text, int64_t nbytes, const int64_t* doc_off, 
 int krca_log_match(const uint8_t* text, int64_t nbytes, const int64_t* doc_off, int64_t ndocs, int64_t* ws,
                    int64_t n_lines, int64_t* line_start, int64_t* line_end, uint32_t* line_mask, int32_t* doc_lines,
                    int32_t* hist, int32_t* examples, int64_t* doc_line0, void* stream) {
-  KRCA_CHECK_ARG(nbytes >= 0 && ndocs >= 1 && n_lines >= 0, "krca_log_match: bad sizes");
-  KRCA_CHECK_ARG(doc_off && ws && doc_lines && hist, "krca_log_match: null pointer");
-  KRCA_CHECK_ARG(((uintptr_t)text & 15) == 0, "krca_log_match: text must be 16-byte aligned");
-  KRCA_CHECK_ARG(n_lines == 0 || (line_start && line_end && line_mask), "krca_log_match: null line arrays");
-  const LogWs w = log_ws(ws, nbytes);
-  const int64_t nt = w.nt;
-  const int64_t* tile = w.tile;
-  const int32_t *chunk = w.chunk, *cdoc = w.cdoc;
-  int64_t* chunk_line0 = w.chunk_line0;
-  int32_t *n_long = w.n_long, *long_q = w.long_q;
-  hipStream_t st = krca::as_stream(stream);
-  if (n_lines > 0) {  // line offsets from the index, then a DFA lane per line (long lines: a wave each)
-    KRCA_HIP(hipMemsetAsync(n_long, 0, sizeof(int32_t), st));
-    hipLaunchKernelGGL(log_lines, dim3((unsigned)nt), dim3(TPB), 0, st, text, nbytes, doc_off, ndocs, cdoc, chunk, tile,
-                       n_lines, line_start, line_end, chunk_line0);
-    KRCA_LAUNCH_CHECK();
-    hipLaunchKernelGGL(log_last_end, dim3(1), dim3(1), 0, st, text, nbytes, doc_off, ndocs, n_lines,
-                       (const int64_t*)nullptr, (int64_t)0, line_end);
-    KRCA_LAUNCH_CHECK();
-    // persistent: the 50 KB table is filled once per workgroup, 3 workgroups per CU
-    const int64_t grid = std::min<int64_t>(krca::ceil_div(n_lines, DFA_TPB), 256 * 3);
-    hipLaunchKernelGGL(log_dfa, dim3((unsigned)grid), dim3(DFA_TPB), 0, st, text, nbytes, n_lines,
-                       (const int64_t*)nullptr, (int64_t)0, (const int64_t*)line_start, (const int64_t*)line_end,
-                       line_mask, long_q, n_long);
-    KRCA_LAUNCH_CHECK();
-    hipLaunchKernelGGL(log_dfa_long, dim3(256), dim3(TPB), 0, st, text, nbytes, (const int64_t*)line_start,
-                       (const int64_t*)line_end, line_mask, (const int32_t*)long_q, (const int32_t*)n_long);
-    KRCA_LAUNCH_CHECK();
-  } else {  // no lines: chunk_line0 = 0 for log_hist
-    KRCA_HIP(hipMemsetAsync(chunk_line0, 0, nt * TPB * sizeof(int64_t), st));
-  }
-  hipLaunchKernelGGL(examples ? log_hist<true> : log_hist<false>, dim3((unsigned)krca::ceil_div(ndocs, TPB)), dim3(TPB),
-                     0, st, doc_off, ndocs, (const int64_t*)chunk_line0, nt * TPB, line_start, line_mask, n_lines,
-                     (const int64_t*)nullptr, (int64_t)0, doc_lines, hist, examples, doc_line0);
-  KRCA_LAUNCH_CHECK();
-  return KRCA_OK;
+  return log_match_seq("krca_log_match", BuiltinMatcher{},
+                       {text, nbytes, doc_off, ndocs, ws, line_start, line_end, line_mask, doc_lines, hist, examples, doc_line0,
+                        stream},
+                       n_lines);
 }
 
 int krca_log_scan(const uint8_t* text, int64_t nbytes, const int64_t* doc_off, int64_t ndocs, int64_t* ws,
                   int64_t line_cap, int64_t* line_start, int64_t* line_end, uint32_t* line_mask, int32_t* doc_lines,
                   int32_t* hist, int32_t* examples, int64_t* doc_line0, int64_t* n_lines_host, void* stream) {
-  KRCA_CHECK_ARG(nbytes >= 0 && ndocs >= 1 && ndocs < INT32_MAX && line_cap >= 0, "krca_log_scan: bad sizes");
-  KRCA_CHECK_ARG(doc_off && ws && doc_lines && hist && n_lines_host, "krca_log_scan: null pointer");
-  KRCA_CHECK_ARG(nbytes == 0 || text, "krca_log_scan: null text");
-  KRCA_CHECK_ARG(((uintptr_t)text & 15) == 0, "krca_log_scan: text must be 16-byte aligned");
-  KRCA_CHECK_ARG(line_cap == 0 || (line_start && line_end && line_mask), "krca_log_scan: null line arrays");
-  const LogWs w = log_ws(ws, nbytes);
-  const int64_t nt = w.nt;
-  int64_t* const tile = w.tile;  // tile[nt] = the line count, on the device
-  hipStream_t st = krca::as_stream(stream);
-  if (nbytes == 0) {
-    // no text (the pointer may be null): every container is empty and no kernel may read text --
-    // the index pass's unconditional piece loads clamp to the last 16-byte block that holds a
-    // byte, and there is none (an empty window faulted there: test_log_scan_degenerate_texts)
-    KRCA_HIP(hipMemsetAsync(tile, 0, (nt + 1) * sizeof(int64_t), st));  // tile bases, the line count
-    KRCA_HIP(hipMemsetAsync(w.chunk_line0, 0, nt * TPB * sizeof(int64_t), st));
-    KRCA_HIP(hipMemsetAsync(doc_lines, 0, ndocs * sizeof(int32_t), st));
-    KRCA_HIP(hipMemsetAsync(hist, 0, ndocs * KRCA_NCAT * sizeof(int32_t), st));
-    if (examples) KRCA_HIP(hipMemsetAsync(examples, 0xFF, ndocs * KRCA_NCAT * 3 * sizeof(int32_t), st));  // -1
-    if (doc_line0) KRCA_HIP(hipMemsetAsync(doc_line0, 0, ndocs * sizeof(int64_t), st));
-    *n_lines_host = 0;
-    return KRCA_OK;
-  }
-  // one launch before the index: the chunk -> container map (every chunk of the text is written
-  // under the doc_off contract; off it, tile_container_starts clamps what it reads), and the zeroed
-  // look-back status words + ticket and long-line count (no memset launches: each dependent
-  // launch costs ~10 us at the front of the scan)
-  hipLaunchKernelGGL(log_chunk_doc, dim3((unsigned)krca::ceil_div(ndocs, TPB)), dim3(TPB), 0, st, doc_off, ndocs,
-                     nbytes, w.cdoc, w.status, 2 * nt + 1, w.n_long);  // status words, ticket
-  KRCA_LAUNCH_CHECK();
-  const int64_t* Ld = tile + nt;  // the line count, on the device (written by the index's last tile)
-  if (krca::tuning().log_fused) {
-    // A/B: the line index and the DFA walk in one pass over the text (KRCA_LOG_FUSED = 1: 32 KiB
-    // tiles, two 512-thread workgroups per CU; 2: 64 KiB tiles, one 1024-thread workgroup per CU);
-    // long lines go to log_dfa_long.  It reads the text once but runs its phases one after the
-    // other per tile (DESIGN §3.3)
-    auto launch = [&](auto cfg) -> int64_t {
-      using CF = decltype(cfg);
-      const int64_t ntf = num_ftiles(nbytes, CF::FTILE);
-      const int64_t resident =
-          krca::resident_workgroups(reinterpret_cast<const void*>(&log_index_match<CF>), CF::FTPB, st, 1);
-      hipLaunchKernelGGL(log_index_match<CF>, dim3((unsigned)std::min<int64_t>(ntf, resident)), dim3(CF::FTPB), 0, st,
-                         text, nbytes, doc_off, ndocs, (const int32_t*)w.cdoc, w.chunk, tile, nt, w.status, w.ticket,
-                         ntf, line_cap, line_start, line_end, line_mask, w.chunk_line0, tile + nt, w.long_q, w.n_long);
-      return ntf;
-    };
-    if (krca::tuning().log_fused == 2) launch(FBig{});
-    else launch(FSmall{});
-    KRCA_LAUNCH_CHECK();
-  } else {  // default (KRCA_LOG_FUSED=0): the line index, then a DFA lane per line re-reading the text
-    // workgroups the stream's device keeps resident (occupancy API, cached per device)
-    const int64_t resident = krca::resident_workgroups(reinterpret_cast<const void*>(&log_index_lines), TPB, st, 4);
-    const int64_t grid_ix = LOG_IDX_PERSIST ? std::min<int64_t>(nt, resident) : nt;
-    hipLaunchKernelGGL(log_index_lines, dim3((unsigned)grid_ix), dim3(TPB), 0, st, text, nbytes, doc_off, ndocs,
-                       (const int32_t*)w.cdoc, w.chunk, tile, w.status, w.ticket, nt, line_cap, line_start, line_end,
-                       w.chunk_line0, tile + nt);
-    KRCA_LAUNCH_CHECK();
-    const int64_t grid = std::max<int64_t>(1, std::min<int64_t>(krca::ceil_div(line_cap, DFA_TPB), 256 * 3));
-    hipLaunchKernelGGL(log_dfa, dim3((unsigned)grid), dim3(DFA_TPB), 0, st, text, nbytes, (int64_t)0, Ld, line_cap,
-                       (const int64_t*)line_start, (const int64_t*)line_end, line_mask, w.long_q, w.n_long);
-    KRCA_LAUNCH_CHECK();
-  }
-  hipLaunchKernelGGL(log_dfa_long, dim3(256), dim3(TPB), 0, st, text, nbytes, (const int64_t*)line_start,
-                     (const int64_t*)line_end, line_mask, (const int32_t*)w.long_q, (const int32_t*)w.n_long);
-  KRCA_LAUNCH_CHECK();
-  hipLaunchKernelGGL(examples ? log_hist<true> : log_hist<false>, dim3((unsigned)krca::ceil_div(ndocs, TPB)), dim3(TPB),
-                     0, st, doc_off, ndocs, (const int64_t*)w.chunk_line0, nt * TPB, line_start, line_mask, (int64_t)0, Ld,
-                     line_cap, doc_lines, hist, examples, doc_line0);
-  KRCA_LAUNCH_CHECK();
-  KRCA_HIP(hipMemcpyAsync(n_lines_host, Ld, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-  KRCA_HIP(hipStreamSynchronize(st));
-  return KRCA_OK;
+  return log_scan_seq("krca_log_scan", BuiltinMatcher{},
+                      {text, nbytes, doc_off, ndocs, ws, line_start, line_end, line_mask, doc_lines, hist, examples, doc_line0,
+                       stream},
+                      line_cap, n_lines_host);
 }
 
 // ---- pattern tables compiled at run time (include/krca.h) ------------------------------------------
@@ -1890,91 +2100,21 @@ int krca_log_match_tables(const uint8_t* text, int64_t nbytes, const int64_t* do
                           const void* tables_dev, int64_t tables_dev_bytes, const krca_log_dims* dims_host, int64_t n_lines,
                           int64_t* line_start, int64_t* line_end, uint32_t* line_mask, int32_t* doc_lines, int32_t* hist,
                           int32_t* examples, int64_t* doc_line0, void* stream) {
-  KRCA_CHECK_ARG(nbytes >= 0 && ndocs >= 1 && n_lines >= 0, "krca_log_match_tables: bad sizes");
-  KRCA_CHECK_ARG(doc_off && ws && doc_lines && hist, "krca_log_match_tables: null pointer");
-  KRCA_CHECK_ARG(((uintptr_t)text & 15) == 0, "krca_log_match_tables: text must be 16-byte aligned");
-  KRCA_CHECK_ARG(n_lines == 0 || (line_start && line_end && line_mask), "krca_log_match_tables: null line arrays");
-  hipStream_t st = krca::as_stream(stream);
-  RtPlan plan;
-  const int rc = rt_plan("krca_log_match_tables", tables_dev, tables_dev_bytes, dims_host, st, plan);
-  if (rc) return rc;
-  const uint8_t* tab = static_cast<const uint8_t*>(tables_dev);
-  const LogWs w = log_ws(ws, nbytes);
-  const int64_t nt = w.nt;
-  if (n_lines > 0) {
-    KRCA_HIP(hipMemsetAsync(w.n_long, 0, sizeof(int32_t), st));
-    hipLaunchKernelGGL(log_lines, dim3((unsigned)nt), dim3(TPB), 0, st, text, nbytes, doc_off, ndocs, (const int32_t*)w.cdoc,
-                       (const int32_t*)w.chunk, (const int64_t*)w.tile, n_lines, line_start, line_end, w.chunk_line0);
-    KRCA_LAUNCH_CHECK();
-    hipLaunchKernelGGL(log_last_end, dim3(1), dim3(1), 0, st, text, nbytes, doc_off, ndocs, n_lines,
-                       (const int64_t*)nullptr, (int64_t)0, line_end);
-    KRCA_LAUNCH_CHECK();
-    if (plan.rsl == 5)
-      rt_launch_walk<5>(plan, st, text, nbytes, n_lines, nullptr, 0, line_start, line_end, line_mask, w.long_q, w.n_long, tab);
-    else
-      rt_launch_walk<6>(plan, st, text, nbytes, n_lines, nullptr, 0, line_start, line_end, line_mask, w.long_q, w.n_long, tab);
-    KRCA_LAUNCH_CHECK();
-  } else {  // no lines: chunk_line0 = 0 for log_hist_rt
-    KRCA_HIP(hipMemsetAsync(w.chunk_line0, 0, nt * TPB * sizeof(int64_t), st));
-  }
-  hipLaunchKernelGGL(examples ? log_hist_rt<true> : log_hist_rt<false>, dim3((unsigned)krca::ceil_div(ndocs, TPB)),
-                     dim3(TPB), 0, st, doc_off, ndocs, (const int64_t*)w.chunk_line0, nt * TPB, line_start, line_mask, n_lines,
-                     (const int64_t*)nullptr, (int64_t)0, doc_lines, hist, examples, doc_line0, (int)plan.dm.ncat);
-  KRCA_LAUNCH_CHECK();
-  return KRCA_OK;
+  return log_match_seq("krca_log_match_tables", RtMatcher(tables_dev, tables_dev_bytes, dims_host),
+                       {text, nbytes, doc_off, ndocs, ws, line_start, line_end, line_mask, doc_lines, hist, examples, doc_line0,
+                        stream},
+                       n_lines);
 }
 
 int krca_log_scan_tables(const uint8_t* text, int64_t nbytes, const int64_t* doc_off, int64_t ndocs, int64_t* ws,
                          const void* tables_dev, int64_t tables_dev_bytes, const krca_log_dims* dims_host, int64_t line_cap,
                          int64_t* line_start, int64_t* line_end, uint32_t* line_mask, int32_t* doc_lines, int32_t* hist,
                          int32_t* examples, int64_t* doc_line0, int64_t* n_lines_host, void* stream) {
-  KRCA_CHECK_ARG(nbytes >= 0 && ndocs >= 1 && ndocs < INT32_MAX && line_cap >= 0, "krca_log_scan_tables: bad sizes");
-  KRCA_CHECK_ARG(doc_off && ws && doc_lines && hist && n_lines_host, "krca_log_scan_tables: null pointer");
-  KRCA_CHECK_ARG(nbytes == 0 || text, "krca_log_scan_tables: null text");
-  KRCA_CHECK_ARG(((uintptr_t)text & 15) == 0, "krca_log_scan_tables: text must be 16-byte aligned");
-  KRCA_CHECK_ARG(line_cap == 0 || (line_start && line_end && line_mask), "krca_log_scan_tables: null line arrays");
-  hipStream_t st = krca::as_stream(stream);
-  RtPlan plan;
-  const int rc = rt_plan("krca_log_scan_tables", tables_dev, tables_dev_bytes, dims_host, st, plan);
-  if (rc) return rc;
-  const uint8_t* tab = static_cast<const uint8_t*>(tables_dev);
-  const int ncat = plan.dm.ncat;
-  const LogWs w = log_ws(ws, nbytes);
-  const int64_t nt = w.nt;
-  int64_t* const tile = w.tile;
-  if (nbytes == 0) {  // no text (the pointer may be null): no kernel may read it; as krca_log_scan
-    KRCA_HIP(hipMemsetAsync(tile, 0, (nt + 1) * sizeof(int64_t), st));
-    KRCA_HIP(hipMemsetAsync(w.chunk_line0, 0, nt * TPB * sizeof(int64_t), st));
-    KRCA_HIP(hipMemsetAsync(doc_lines, 0, ndocs * sizeof(int32_t), st));
-    KRCA_HIP(hipMemsetAsync(hist, 0, ndocs * ncat * sizeof(int32_t), st));
-    if (examples) KRCA_HIP(hipMemsetAsync(examples, 0xFF, ndocs * ncat * 3 * sizeof(int32_t), st));  // -1
-    if (doc_line0) KRCA_HIP(hipMemsetAsync(doc_line0, 0, ndocs * sizeof(int64_t), st));
-    *n_lines_host = 0;
-    return KRCA_OK;
-  }
-  hipLaunchKernelGGL(log_chunk_doc, dim3((unsigned)krca::ceil_div(ndocs, TPB)), dim3(TPB), 0, st, doc_off, ndocs,
-                     nbytes, w.cdoc, w.status, 2 * nt + 1, w.n_long);  // the map; status words, ticket, long-line count zeroed
-  KRCA_LAUNCH_CHECK();
-  const int64_t* Ld = tile + nt;  // the line count, on the device
   // always the two-pass path (KRCA_LOG_FUSED does not apply): the line index, then the walk re-reading the text
-  const int64_t resident = krca::resident_workgroups(reinterpret_cast<const void*>(&log_index_lines), TPB, st, 4);
-  const int64_t grid_ix = LOG_IDX_PERSIST ? std::min<int64_t>(nt, resident) : nt;
-  hipLaunchKernelGGL(log_index_lines, dim3((unsigned)grid_ix), dim3(TPB), 0, st, text, nbytes, doc_off, ndocs,
-                     (const int32_t*)w.cdoc, w.chunk, tile, w.status, w.ticket, nt, line_cap, line_start, line_end,
-                     w.chunk_line0, tile + nt);
-  KRCA_LAUNCH_CHECK();
-  if (plan.rsl == 5)
-    rt_launch_walk<5>(plan, st, text, nbytes, 0, Ld, line_cap, line_start, line_end, line_mask, w.long_q, w.n_long, tab);
-  else
-    rt_launch_walk<6>(plan, st, text, nbytes, 0, Ld, line_cap, line_start, line_end, line_mask, w.long_q, w.n_long, tab);
-  KRCA_LAUNCH_CHECK();
-  hipLaunchKernelGGL(examples ? log_hist_rt<true> : log_hist_rt<false>, dim3((unsigned)krca::ceil_div(ndocs, TPB)),
-                     dim3(TPB), 0, st, doc_off, ndocs, (const int64_t*)w.chunk_line0, nt * TPB, line_start, line_mask,
-                     (int64_t)0, Ld, line_cap, doc_lines, hist, examples, doc_line0, ncat);
-  KRCA_LAUNCH_CHECK();
-  KRCA_HIP(hipMemcpyAsync(n_lines_host, Ld, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-  KRCA_HIP(hipStreamSynchronize(st));
-  return KRCA_OK;
+  return log_scan_seq("krca_log_scan_tables", RtMatcher(tables_dev, tables_dev_bytes, dims_host),
+                      {text, nbytes, doc_off, ndocs, ws, line_start, line_end, line_mask, doc_lines, hist, examples, doc_line0,
+                       stream},
+                      line_cap, n_lines_host);
 }
 
 #ifdef LOG_TIMING

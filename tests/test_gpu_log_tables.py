@@ -13,7 +13,7 @@ import pytest
 import agent_cases as A
 import custom_pattern_sets as S
 from guarded import GuardedEngine, run_poisons
-from krca import native, synth
+from krca import logdfa, native, synth
 from krca.agents.logs import pack_documents
 
 pytestmark = pytest.mark.gpu
@@ -34,10 +34,11 @@ def one_call(e, blob, off, tables=None):
 
 
 def two_calls(e, blob, off, tables):
-    """krca_log_index, then krca_log_match_tables into line arrays of exactly the line count."""
+    """krca_log_index, then krca_log_match_tables (tables None: krca_log_match, the compiled-in
+    patterns) into line arrays of exactly the line count."""
     t = e.torch
     text, offd = e.upload_blob(blob), e._dev(np.asarray(off, np.int64))
-    nbytes, D, nc = len(blob), len(off) - 1, tables.ncat
+    nbytes, D, nc = len(blob), len(off) - 1, tables.ncat if tables is not None else native.NCAT
     ws = e._workspace("logidx", 8 * e.lib.krca_log_index_size(nbytes))
     nl = t.empty(1, dtype=t.int64, device=e.device)
     native._check(e.lib.krca_log_index(e.ptr(text), nbytes, e.ptr(offd), D, e.ptr(ws), e.ptr(nl), e._stream()),
@@ -46,10 +47,14 @@ def two_calls(e, blob, off, tables):
     new = lambda dt, *shape: t.empty(shape, dtype=dt, device=e.device)  # noqa: E731
     r = dict(line_start=new(t.int64, L), line_end=new(t.int64, L), line_mask=new(t.int32, L), doc_lines=new(t.int32, D),
              doc_line0=new(t.int64, D), hist=new(t.int32, D, nc), examples=new(t.int32, D, nc, 3))
-    native._check(e.lib.krca_log_match_tables(
-        e.ptr(text), nbytes, e.ptr(offd), D, e.ptr(ws), e.ptr(tables.dev), tables.dev.numel(), ctypes.byref(tables.dims),
-        L, e.ptr(r["line_start"]), e.ptr(r["line_end"]), e.ptr(r["line_mask"]), e.ptr(r["doc_lines"]), e.ptr(r["hist"]),
-        e.ptr(r["examples"]), e.ptr(r["doc_line0"]), e._stream()), "krca_log_match_tables")
+    out = (L, e.ptr(r["line_start"]), e.ptr(r["line_end"]), e.ptr(r["line_mask"]), e.ptr(r["doc_lines"]), e.ptr(r["hist"]),
+           e.ptr(r["examples"]), e.ptr(r["doc_line0"]), e._stream())
+    if tables is None:
+        native._check(e.lib.krca_log_match(e.ptr(text), nbytes, e.ptr(offd), D, e.ptr(ws), *out), "krca_log_match")
+    else:
+        native._check(e.lib.krca_log_match_tables(
+            e.ptr(text), nbytes, e.ptr(offd), D, e.ptr(ws), e.ptr(tables.dev), tables.dev.numel(), ctypes.byref(tables.dims),
+            *out), "krca_log_match_tables")
     return {k: r[k].cpu().numpy().copy() for k in KEYS}
 
 
@@ -149,6 +154,76 @@ def test_golden_line_masks(eng, name):
     assert np.array_equal(r["examples"], native.example_ids(r["line_mask"], r["doc_line0"], r["doc_lines"], len(pats)))
 
 
+# ---- the histogram kernel: one for every category count -------------------------------------------------
+HIST_SIZES = (0, 1, 32, 33, 64, 65, 200)   # lines: none; one; the lane loop's last size and the wave path's first;
+#                                            one 64-line round, one line past it, several rounds
+HIST_SPOTS = (0, 63, 64, 255, 256, 299)    # block lanes 0, 63, 64 and 255; the second block's first; the last container
+
+
+def _hist_docs(lits_by_cat, rot):
+    """300 containers (a full 256-lane block and one of 44).  Container HIST_SPOTS[p] holds
+    HIST_SIZES[(p + rot) % 7] lines, so the seven rotations put every size at every spot; the others hold
+    1-3 lines.  A container of 32 lines or more matches category a on every third line and b on every
+    fourth (both more than three times: the example tables fill up, some lines carry both) and, at 200
+    lines, a third on lines 40, 90, 140 and 190 (its examples come from three 64-line rounds)."""
+    rng = np.random.default_rng(100 + rot)
+    nc = len(lits_by_cat)
+    docs = []
+    for d in range(300):
+        if d in HIST_SPOTS:
+            p = HIST_SPOTS.index(d)
+            n, a = HIST_SIZES[(p + rot) % 7], (3 * p + rot) % nc  # (every size meets low and high categories)
+            lines = []
+            for i in range(n):
+                ln = "l%d" % i
+                if i % 3 == 1:
+                    ln += " " + lits_by_cat[a]
+                if i % 4 == 2:
+                    ln += " " + lits_by_cat[(a + 1) % nc]
+                if nc > 3 and i % 50 == 40:
+                    ln += " " + lits_by_cat[(a + 3) % nc]
+                lines.append(ln)
+        else:
+            lines = [("s%d " % d) + (lits_by_cat[int(rng.integers(nc))] if rng.random() < 0.5 else "quiet")
+                     for _ in range(int(rng.integers(1, 4)))]
+        docs.append("\n".join(lines) + ("\n" if d % 2 and lines else ""))
+    return docs
+
+
+@pytest.mark.parametrize("name", ["S13", "C", "B"])
+def test_hist_every_container_size_at_every_block_position(eng, name):
+    """log_hist<DENSE, Cats> with the category count compiled in (S13 through krca_log_scan /
+    krca_log_match) and as an argument (C: 3, B: 16), dense example table, through the one-call scan and
+    through index + match: doc_lines, counts and the three example lines of every container equal re's,
+    and the example bits of the line masks give the same table."""
+    pats = S.SETS[name]
+    nc = len(pats)
+    tb = None if name == "S13" else eng.log_tables(pats)
+    lits = iter(S.literals(pats))  # one per alternative, in pattern order: each category's first
+    lits_by_cat = [[next(lits) for _ in logdfa.parse(cat, rx)][0] for cat, rx in pats]
+    eng._log_cap = max(eng._log_cap, 4096)  # the one call is not to fall back to the match call
+    for rot in range(7):
+        docs = _hist_docs(lits_by_cat, rot)
+        want = [S.re_hist(pats, text) for text in docs]
+        for d, n in zip(HIST_SPOTS, (HIST_SIZES[(p + rot) % 7] for p in range(6))):
+            assert want[d][0] == n
+            if n >= 32:  # more than three matching lines in two categories or more, none in another
+                assert sum(h > 3 for h in want[d][1]) >= 2 and min(want[d][1]) == 0, (rot, d, want[d][1])
+        blob, off = pack_documents(docs)
+        for got in (one_call(eng, blob, off, tb), two_calls(eng, blob, off, tb)):
+            assert got["hist"].shape == (300, nc) and got["examples"].shape == (300, nc, 3)
+            assert got["doc_lines"].tolist() == [w[0] for w in want]
+            assert got["hist"].tolist() == [w[1] for w in want]
+            text_of = [bytes(blob[s:e]).decode() for s, e in zip(got["line_start"].tolist(), got["line_end"].tolist())]
+            for d in range(300):
+                for c in range(nc):
+                    ids = [i for i in got["examples"][d, c].tolist() if i >= 0]
+                    assert [text_of[i] for i in ids] == want[d][2][c], (rot, d, c)
+                    assert got["examples"][d, c].tolist() == ids + [-1] * (3 - len(ids)), (rot, d, c)
+            assert np.array_equal(got["examples"],
+                                  native.example_ids(got["line_mask"], got["doc_line0"], got["doc_lines"], nc))
+
+
 # ---- long lines: the warm-up is the set's, not the compiled walk's 23 ------------------------------------
 def _long_line(nbytes, k, alt, filler, back):
     """A line of about nbytes bytes (filler code points of one width) in which `alt` starts `back` of its
@@ -165,7 +240,7 @@ def _long_line(nbytes, k, alt, filler, back):
 
 @pytest.mark.parametrize("multibyte", [False, True])
 def test_long_lines_longest_alternative_across_every_segment_boundary(eng, multibyte):
-    """Lines of 1025 to 8000 bytes go to log_dfa_long_rt (a wave per line, 64 segments).  The 40 code
+    """Lines of 1025 to 8000 bytes go to log_dfa_long (a wave per line, 64 segments).  The 40 code
     point alternative is placed to straddle each of the 63 inner segment boundaries in turn (8000-byte
     lines; shorter ones fold the boundary index), starting 39, 30 and 2 code points before it: a segment
     warmed up over only 23 code points misses the first two."""

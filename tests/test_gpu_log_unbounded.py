@@ -1,6 +1,6 @@
 """Log scan with unbounded quantifiers in run-time pattern sets on an MI355X:
 NativeEngine.log_tables(patterns, unbounded=True), the long-line kernel that carries the DFA state
-from segment to segment (log_dfa_long_carry_rt, taken for tables with KRCA_LOG_FLAG_CARRY),
+from segment to segment (log_dfa_long<TabRt, CARRY>, taken for tables with KRCA_LOG_FLAG_CARRY),
 LogsAgent(unbounded=True) and StreamingRCA(log_tables=).
 
 Expected values: Python's ``re`` per line (the reference's definition, ref:agents/logs_agent.py:147-149),
@@ -111,7 +111,7 @@ def _long40_docs(multibyte):
 @pytest.mark.parametrize("case", ["long40", "long40-multibyte", "s13-golden", "s13-long"])
 def test_carry_flag_forced_on_fixed_sets_is_byte_equal(eng, case):
     """The same tables uploaded with KRCA_LOG_FLAG_CARRY forced on (LogTables.image(flags=)): long lines
-    go through log_dfa_long_carry_rt and every output array equals the unflagged tables' byte for byte."""
+    go through the carrying log_dfa_long and every output array equals the unflagged tables' byte for byte."""
     if case.startswith("long40"):
         pats, docs = _long40_docs(case.endswith("multibyte"))
     else:

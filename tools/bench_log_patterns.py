@@ -1,13 +1,17 @@
 #!/usr/bin/env python3
 """Cost of run-time pattern tables against the compiled-in log matcher.
 
-Corpus: the C5 window of tools/bench_stream.py (1M containers, ~2.45M lines).  Each round times, in
-a fresh random order, one scan per variant between HIP events:
+Corpus: the C5 window of tools/bench_stream.py (1M containers, ~2.45M lines) and 32 containers of
+four lines of 4 to 7 KiB, so that the wave-per-line kernel has work.  Each round times, in a fresh
+random order, one scan per variant between HIP events:
   compiled     krca_log_scan (the 13 patterns in constant memory)
   tables_S13   krca_log_scan_tables, the same 13 patterns compiled at run time (32 columns)
   tables_B     krca_log_scan_tables, 16 categories / 36 symbols / 543 states (64 columns)
-  parent       krca_log_scan of a second library (--parent-lib: the parent commit's build), in the
-               same rounds: the compiled path must not move (the 3 % gate of DESIGN §3.7, on medians)
+  tables_U1    krca_log_scan_tables, S13 with exception -> Exception.*at (tests/unbounded_pattern_sets.py:
+               the carry flag, 737 states)
+  parent, parent_S13, parent_B, parent_U1
+               the same four through a second library (--parent-lib: the parent commit's build), in the
+               same rounds: no path may move (the 3 % gate of DESIGN §3.7, on medians; ratio_vs_parent)
 Medians and p95 go to --out as JSON.  Per-kernel times: run it once under
 `rocprofv3 --kernel-trace --stats -- python tools/bench_log_patterns.py --rounds 3 --warmup 1`.
 """
@@ -31,7 +35,7 @@ def main():
     ap.add_argument("--lines", type=int, default=2_500_000)
     ap.add_argument("--rounds", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--parent-lib", help="a second libkrca.so whose krca_log_scan is timed in the same rounds")
+    ap.add_argument("--parent-lib", help="a second libkrca.so whose scans are timed in the same rounds")
     ap.add_argument("--out")
     a = ap.parse_args()
     import numpy as np
@@ -42,39 +46,53 @@ def main():
     eng = native.NativeEngine()
     t0 = time.time()
     docs = synth.make_log_corpus(a.containers, lines_per_doc=a.lines / a.containers, seed=1, hazard_rate=0.001)
+    long_line = lambda i: ("retry 12/3 Exception in thread " + "q" * 480) * (8 + i % 7) + " at line %d" % i  # noqa: E731
+    docs += ["\n".join(long_line(4 * d + j) for j in range(4)) for d in range(32)]
     blob, off = pack_documents(docs)
     del docs
     native.check_doc_off(off, len(blob))
     text, offd = eng.upload_blob(blob), eng._dev(off)
     gen_s = time.time() - t0
     s13 = list(patterns.ERROR_PATTERNS)
+    u1 = [(n, r"Exception.*at" if n == "exception" else p) for n, p in s13]
     compile_s = {}
     for name, pats in (("S13", s13), ("B", s13 + SET_B)):
         logdfa._CACHE.clear()
         t0 = time.time()
         logdfa.compile_patterns(pats)
         compile_s[name] = round(time.time() - t0, 3)
-    tb13, tbB = eng.log_tables(s13), eng.log_tables(s13 + SET_B)
-    variants = {"compiled": (eng, None), "tables_S13": (eng, tb13), "tables_B": (eng, tbB)}
+    tables = lambda e: {"S13": e.log_tables(s13), "B": e.log_tables(s13 + SET_B), "U1": e.log_tables(u1, unbounded=True)}  # noqa: E731
+    tabs = tables(eng)
+    tb13, tbB = tabs["S13"], tabs["B"]
+    variants = {"compiled": (eng, None), **{"tables_" + k: (eng, t) for k, t in tabs.items()}}
     if a.parent_lib:
         import ctypes
         par = native.NativeEngine()
-        par.lib = ctypes.CDLL(os.path.abspath(a.parent_lib))  # (an older build: it lacks the tables exports)
+        par.lib = ctypes.CDLL(os.path.abspath(a.parent_lib))
         for name, (res_t, arg_t) in native.SIGNATURES.items():
             fn = getattr(par.lib, name, None)
             if fn is not None:
                 fn.restype, fn.argtypes = res_t, arg_t
-        variants["parent"] = (par, None)
-    # same results first: S13 by tables equals the compiled path; the parent's too
+        variants.update({"parent": (par, None), **{"parent_" + k: (par, t) for k, t in tables(par).items()}})
+    # same results first: S13 by tables equals the compiled path, B and U1 in the categories they share with
+    # it, and every variant of the parent equals this build's byte for byte
     ref = eng.log_scan_device(text, offd, validate=False)
     n_lines = ref["n_lines_total"]
+    assert int((ref["line_end"] - ref["line_start"] > 1024).sum().item()) >= 128  # the long-line kernel has work
+    mine = {}
     for name, (e, tb) in variants.items():
         r = e.log_scan_device(text, offd, validate=False, **({"tables": tb} if tb is not None else {}))
         assert r["n_lines_total"] == n_lines, name
-        if name != "tables_B":
-            assert torch.equal(r["hist"], ref["hist"]) and torch.equal(r["line_mask"], ref["line_mask"]), name
+        kind = name.split("_")[-1].replace("parent", "compiled")  # compiled, S13, B or U1
+        if kind in ("B", "U1"):
+            same = [c for c, (p, q) in enumerate(zip(tb.tables.patterns, s13)) if tuple(p) == tuple(q)]
+            assert len(same) == (13 if kind == "B" else 12) and torch.equal(r["hist"][:, same], ref["hist"][:, same]), name
         else:
-            assert torch.equal(r["hist"][:, :13], ref["hist"]), name
+            assert torch.equal(r["hist"], ref["hist"]) and torch.equal(r["line_mask"], ref["line_mask"]), name
+        if e is eng:
+            mine[kind] = r
+        else:
+            assert torch.equal(r["hist"], mine[kind]["hist"]) and torch.equal(r["line_mask"], mine[kind]["line_mask"]), name
     times = {k: [] for k in variants}
     rng = np.random.default_rng(0)
     for rnd in range(a.warmup + a.rounds):
@@ -100,6 +118,9 @@ def main():
     if stat:
         c = stat["compiled"]["median_us"]
         res["ratio_vs_compiled"] = {k: round(v["median_us"] / c, 4) for k, v in stat.items()}
+        if a.parent_lib:  # this build over the parent's, pair by pair
+            res["ratio_vs_parent"] = {k: round(stat[k]["median_us"] / stat[k.replace("compiled", "parent").replace("tables", "parent")]
+                                               ["median_us"], 4) for k in stat if not k.startswith("parent")}
     print(json.dumps(res))
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)

@@ -12,7 +12,7 @@ a fresh random order, one krca_log_scan_tables call per variant between HIP even
 --long: what carrying the state costs on lines over 1 KiB.  Corpora of 8 KiB and of 64 KiB lines, and
 one single 64 KiB line, each "best" (no state survives a segment boundary) and "worst" ("error" in the
 first segment of every line: 63 rounds, one serial walk of the line).  Each text is scanned with U4
-(log_dfa_long_carry_rt) and with F4, a fixed-length set of the same shape (log_dfa_long_rt), --reps
+(log_dfa_long<TabRt, true>) and with F4, a fixed-length set of the same shape (log_dfa_long<TabRt, false>), --reps
 times, in that order; whole-scan times between HIP events.  The schedule is printed with the result.
 Per-kernel times: run `rocprofv3 --kernel-trace --stats -- python tools/bench_log_unbounded.py --long`
 in a run of its own, then `--long --trace <..._kernel_trace.csv> --schedule <result json>` assigns the
@@ -22,6 +22,7 @@ import argparse
 import csv
 import json
 import os
+import re
 import sys
 import time
 
@@ -105,8 +106,8 @@ def merge_trace(a, np):
     for s in res["schedule"]:
         mine = rows[k:k + s["dispatches"]]
         k += s["dispatches"]
-        want = "log_dfa_long_carry_rt" if s["variant"] == "carry_U4" else "log_dfa_long_rt"
-        assert all(want in r["Kernel_Name"] for r in mine), (s, mine[0]["Kernel_Name"])
+        want = "true>" if s["variant"] == "carry_U4" else "false>"  # log_dfa_long<TabRt<RSL>, CARRY>
+        assert all(re.search(r"log_dfa_long<.*TabRt<\d>, " + want, r["Kernel_Name"]) for r in mine), (s, mine[0]["Kernel_Name"])
         us = [(int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3 for r in mine[1:]]  # (the first: warm-up)
         res["cases"][s["case"]][s["variant"]]["kernel"] = stats(np, us)
     for case, c in res["cases"].items():
